@@ -6,8 +6,10 @@ producing gradients for every Gaussian and skeleton parameter.
 densification or logging.  N ranks = N independent frames per step (weak scaling) followed by one
 RCCL all-reduce of the flat gradient buffer of the replicated parameters.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-timed live with HIP events on its launch stream) and `cpu_baseline` (the CPU oracle timed on the host cores).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `ms_per_step` over exactly --steps timed
+steps, ...).  `--full` adds everything else the benchmark measures and checks: `roofline` (dominant kernel, timed live with
+HIP events on its launch stream), `cpu_baseline` (the CPU oracle timed on the host cores) with the parity of the timed
+frame against it, and the secondary timings.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -338,7 +340,47 @@ def dense_scene_timing(dev, steps=50):
 
 
 LISTS = "canonical"  # (--lists)
-MIN_TIMED_STEPS = 100  # the timed region covers at least this many steps, whatever --steps is (blocks of exactly --steps)
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: the whole dump
+DUMP_ROWS = 1 << 16  # --dump-outputs: per-Gaussian arrays of a larger scene are written on a seeded sample of this many rows
+
+
+def dump_outputs(path, pkg, gm, sw):
+    """``--dump-outputs``: what the last timed step handed its caller — the tensors of the render package (the screen-space
+    gradient included) and the gradient of every parameter — one ``<name>.npy`` each, float32 (integer and boolean arrays as
+    float64).  The same seeded sample of rows is taken from every per-Gaussian array, so that the dump stays within
+    DUMP_BYTES_MAX; the inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    n = gm.get_xyz.shape[0]
+    rows = None
+    if n > DUMP_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(WORKLOAD["seed"]))[:DUMP_ROWS].sort().values
+    arrays = {}
+    for k in dict.keys(pkg):
+        v = dict.__getitem__(pkg, k)
+        if k == "bg_color":  # (handed back unchanged: an input of the step)
+            continue
+        if k == "viewspace_points":  # (an eagerly issued step: the leaf holds zeros, its gradient is the output)
+            k, v = "viewspace_points_grad", v.grad
+        arrays[k] = v
+    for k, p in zip(("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"), gm.parameters()):
+        arrays["grad_" + k] = p.grad
+    arrays["grad_node_radius"] = sw._node_radius.grad
+    for k, p in sw.pose_net.named_parameters():
+        arrays["grad_pose_net." + k] = p.grad
+    host = {}
+    for k, v in arrays.items():
+        if not isinstance(v, torch.Tensor):
+            continue
+        v = v.detach()
+        if rows is not None and v.dim() >= 1 and v.shape[0] == n:
+            v = v[rows.to(v.device)]
+        host[k] = v.cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES_MAX:  # (checked before anything is written: no partial dump)
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_BYTES_MAX))
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _tight(other=False):
@@ -999,12 +1041,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: the per-kernel roofline leg, the secondary timings, the CPU baseline "
+                         "and the timed frame's parity against the CPU oracle (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (image, screen-space and parameter gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity of the timed frame against it")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch eagerly instead of replaying a hipGraph")
-    ap.add_argument("--profile-all", action="store_true", help="print a per-kernel event-timer table to stderr")
+    ap.add_argument("--profile-all", action="store_true", help="--full: print the per-kernel event-timer table to stderr")
     ap.add_argument("--exchange", choices=("rows", "dense"), default="rows",
                     help="N > 1: gradient-row exchange (packed rows of the Gaussians with a gradient) or the dense two-phase all-reduce")
-    ap.add_argument("--metric-only", action="store_true", help="skip the secondary timings (train step, heads, next rows, dense scene)")
+    ap.add_argument("--metric-only", action="store_true", help="--full: skip the secondary timings (train step, heads, next rows, dense scene)")
     ap.add_argument("--exchange-graph", choices=("auto", "on", "off"), default="auto",
                     help="N > 1: capture the whole data-parallel step (frame + pack + collectives + unpack) as ONE hipGraph; "
                          "auto = when a probe (child processes, own rendezvous) shows that RCCL collectives survive a capture here")
@@ -1018,6 +1065,8 @@ def main():
     ap.add_argument("--scene", choices=("headline", "dense"), default="headline", help=argparse.SUPPRESS)
     ap.add_argument("--capture-probe-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global LISTS
     LISTS = args.lists
     if args.exchange_path_child:
@@ -1078,6 +1127,7 @@ def main():
     # the gradient-row exchange (default): only the Gaussians that received a gradient travel (csrc/exchange.hip); the dense
     # two-phase all-reduce is used when asked for, or when so many rows are touched that it moves fewer bytes per link
     rows = None
+    rows_verified = False  # (the row exchange compared with a plain all-reduce: verify_rows_exchange)
     if world > 1 and args.exchange == "rows":
         rows = SparseRowExchange([v.view(w["N"], -1) for v in bucket.views[:n_rows]], rest=bucket.flat[bucket.offsets[n_rows]:],
                                  capacity=max(1024, w["N"] // 8))
@@ -1146,6 +1196,7 @@ def main():
                                                              and captured_collectives_work(rank, world, local_rank, dev))
                 if use_graph:
                     verify_rows_exchange(gf, rows, world)
+                    rows_verified = True
                     # the whole step as ONE graph: frame (a) -> pack -> all-gather on the communication stream -> frame (b) ->
                     # all-reduce of the skeleton's gradients -> unpack, collectives included (their first eager calls are above)
                     gf = GraphedFrame(gm, sw, cam, torch.zeros(3, device=dev), params, split_backward=True, sparse_grad_rows=True, tight_lists=_tight())
@@ -1157,9 +1208,6 @@ def main():
                     torch.cuda.synchronize()
                     assert gf.check() == R and rows.check()
 
-    names = [lib.riggs_prof_name(i).decode() for i in range(lib.riggs_prof_count())]
-    eager_step = make_step(cam, gm, sw, gimg, arena, 1, bucket)  # profiling leg: rank 0 alone, so NO collective inside
-
     def barrier():
         if world > 1:
             dist.barrier()
@@ -1167,23 +1215,17 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # EXACTLY --steps steps between a barrier + synchronize on both sides — as many such blocks, back to back, as it takes to
-    # have timed at least MIN_TIMED_STEPS steps (a 20-step region of this workload is 7 ms: one scheduling hiccup of the host is
-    # a tenth of it).  ms_per_step is the MEAN over all blocks, not the best one; every block's figure is in ``timed_blocks``.
-    n_blocks = max(1, -(-MIN_TIMED_STEPS // max(args.steps, 1)))
-    block_s = []
-    for _ in range(n_blocks):
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        barrier()
-        block_s.append(time.perf_counter() - t0)
-    if world > 1:  # (per block: the slowest rank's clock)
-        tb = torch.tensor(block_s, device=dev, dtype=torch.float64)
+    # EXACTLY --steps steps between a barrier + synchronize on both sides
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        last = step()
+    barrier()
+    elapsed = time.perf_counter() - t0
+    if world > 1:  # (the slowest rank's clock)
+        tb = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tb, op=dist.ReduceOp.MAX)
-        block_s = [float(v) for v in tb.tolist()]
-    elapsed = sum(block_s) / n_blocks  # of ONE block of --steps steps
+        elapsed = float(tb.item())
     pose_timeouts = 0
     if not args.no_graph:
         # (outside the timed region) the device-side status words of the replays just timed: PoseMLP hand-off time-outs, the
@@ -1207,13 +1249,16 @@ def main():
         assert rows_ok or rows.invalid_frame, "a gradient-row segment overflowed inside the timed region (that step was not exchanged)"
         if rows.invalid_frame:
             pose_timeouts = max(pose_timeouts, 1)
-        if not gf.exchange_in_graph:  # (with --exchange-graph the same comparison ran before the step was captured)
+        if args.full and not gf.exchange_in_graph:  # (with --exchange-graph the same comparison ran before the step was captured)
             verify_rows_exchange(gf, rows, world)
+            rows_verified = True
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, gm, sw)
 
     # the frame that was just timed (static buffers of the graph / the last eager step): its image and gradients are
     # compared with the CPU oracle at this size in the cpu_baseline leg below
     hip_image = hip_grads = hip_pose = hip_deformed = hip_pose_grads = sw_snapshot = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         last = step()
         torch.cuda.synchronize()
         pnames = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation", "node_radius")
@@ -1236,7 +1281,9 @@ def main():
     # (riggs_prof_* in include/riggs_hip.h), over eagerly issued steps of the same workload.
     import ctypes as C
     table = {}
-    if rank == 0:
+    if args.full and rank == 0:
+        names = [lib.riggs_prof_name(i).decode() for i in range(lib.riggs_prof_count())]
+        eager_step = make_step(cam, gm, sw, gimg, arena, 1, bucket)  # profiling leg: rank 0 alone, so NO collective inside
         tot, cnt = C.c_float(), C.c_int32()
         for _ in range(3):
             eager_step()
@@ -1303,6 +1350,26 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * args.steps / elapsed
+        out = {
+            "metric": "train iters/sec (deform+raster fwd+bwd), 300k Gaussians @800x800",
+            "value": round(value, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "pose_handoff_timeouts_rank0": pose_timeouts,
+            "config": {"workload": "300k Gaussians / 24-joint skeleton / 800x800, LBS-only, SH degree 3, anisotropic, "
+                                   "one frame per GPU per step", "num_gaussians": w["N"], "num_joints": w["J"],
+                       "image": [w["H"], w["W"]], "tile_instances_R": R,
+                       "tile_lists": "tight: rectangles cut by the alpha >= 1/255 box at emission (riggs_raster_cfg.tight_lists; same image and "
+                                     "gradients, --full checks the parity)" if LISTS == "tight" else "canonical: upstream's ceil(3 sigma) squares (the library default)",
+                       "parallelism": "frames x%d" % world, "exchange": None if world == 1 else exchange_label,
+                       "launch": "eager" if args.no_graph else "hipGraph replay",
+                       "gradient_rows": "every row written" if (args.no_graph or not gf.sparse_outputs) else
+                       "rows without a gradient now and in the previous replay are not rewritten (they hold their zeros); --full "
+                       "compares the timed frame's gradients with the oracle"},
+        }
+        if not args.full:
+            print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
         N, HW, Bn = w["N"], w["H"] * w["W"], w["J"] - 1
         # ALGORITHMIC bytes per launch of each kernel (DESIGN.md "Kernels and rooflines")
         alg_bytes = {
@@ -1398,24 +1465,7 @@ def main():
         moved_ctr = None
         if all(("read_bytes_x2_corrected" in pm.get(k, {}) and "write_bytes" in pm.get(k, {})) for k in per_step_launches):
             moved_ctr = int(sum(n * (pm[k]["read_bytes_x2_corrected"] + pm[k]["write_bytes"]) for k, n in per_step_launches.items()))
-        out = {
-            "metric": "train iters/sec (deform+raster fwd+bwd), 300k Gaussians @800x800",
-            "value": round(value, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "pose_handoff_timeouts_rank0": pose_timeouts,
-            "timed_blocks": {"blocks": n_blocks, "steps_each": args.steps, "ms_per_step": [round(b / args.steps * 1e3, 4) for b in block_s],
-                             "note": "ms_per_step / value are the MEAN over these back-to-back blocks of exactly --steps steps"},
-            "config": {"workload": "300k Gaussians / 24-joint skeleton / 800x800, LBS-only, SH degree 3, anisotropic, "
-                                   "one frame per GPU per step", "num_gaussians": w["N"], "num_joints": w["J"],
-                       "image": [w["H"], w["W"]], "tile_instances_R": R,
-                       "tile_lists": "tight: rectangles cut by the alpha >= 1/255 box at emission (riggs_raster_cfg.tight_lists; same image and "
-                                     "gradients, parity below)" if LISTS == "tight" else "canonical: upstream's ceil(3 sigma) squares (the library default)",
-                       "parallelism": "frames x%d" % world, "exchange": None if world == 1 else exchange_label,
-                       "launch": "eager" if args.no_graph else "hipGraph replay",
-                       "gradient_rows": "every row written" if (args.no_graph or not gf.sparse_outputs) else
-                       "rows without a gradient now and in the previous replay are not rewritten (they hold their zeros); the timed "
-                       "frame's gradients are compared with the oracle below"},
+        out.update({
             # The dominant kernel is a compositing kernel: SURVEY.md §8-d bounds those by vector issue, not by HBM.  `achieved /
             # peak / frac` stay the HBM numbers from ALGORITHMIC bytes (the contract's definition); `bound` says what actually
             # limits the kernel, `frac_hbm_counter_bytes` prices the bytes the PMC counters saw, `valu` the issue time.
@@ -1435,7 +1485,9 @@ def main():
                                    "depth sort of N keys + a counting sort by tile: the two 'moved' figures are what the step's kernels "
                                    "actually read and write (their own algorithmic bytes; the PMC counters of profiles/kernel_counters.json)"},
             "kernels": per_kernel, "kernels_ms": table, "kernels_in_timed_graph": graph_nodes,
-        }
+        })
+        if world > 1:
+            out["rows_exchange_verified"] = rows_verified
         if world == 1 and not args.metric_only:
             out["eager_api"] = eager_api_timing(cam, gm, sw, gimg)
         if world == 1 and not args.no_graph and not args.metric_only:

@@ -444,18 +444,20 @@ def test_frame_entry_equals_the_two_calls_and_the_oracle(with_mask, extra_heads)
     U.assert_close(img1.cpu().numpy(), out_o["color"], "frame entry image vs oracle", U.REL_TOL, 1e-3)
 
 
-def test_bench_contract_single_and_two_ranks():
-    """bench.py end to end on a tiny scene: the N = 1 JSON line carries every field of the contract (roofline, cpu_baseline,
-    train_step), and the 2-rank launch (the driver's torch.distributed.run command line; gloo stands in for RCCL on a
-    1-GPU box) completes — no collective is ever issued by a subset of the ranks — and reports the whole-job aggregate."""
+def test_bench_contract_single_and_two_ranks(tmp_path):
+    """bench.py end to end on a tiny scene: the N = 1 --full JSON line carries every field of the contract (roofline,
+    cpu_baseline, train_step); a plain run reports the headline alone and dumps the same outputs as the --full run; and the
+    2-rank launch (the driver's torch.distributed.run command line; gloo stands in for RCCL on a 1-GPU box) completes — no
+    collective is ever issued by a subset of the ranks — and reports the whole-job aggregate."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RIGGS_BENCH_TEST_WORKLOAD="4000,8,96,112", MASTER_ADDR="127.0.0.1")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2"], cwd=root, env=env, capture_output=True, text=True,
-                       timeout=600)
+    full_dir, plain_dir = str(tmp_path / "full"), str(tmp_path / "plain")
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--full", "--dump-outputs", full_dir], cwd=root,
+                       env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -488,6 +490,22 @@ def test_bench_contract_single_and_two_ranks():
     dx = ex["dense_scene"]
     assert "error" not in dx, dx
     assert dx["rows_needed"] > 0 and dx["segment_MB"] > 0 and dx["ms"] > 0 and "opaque" in dx["scene"]
+    # a plain run: the headline alone, exactly --steps timed steps, and what its last step computed from the same seeded inputs
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--dump-outputs", plain_dir], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    p = json.loads(r.stdout.strip().splitlines()[-1])
+    assert p["steps"] == 5 and p["ms_per_step"] > 0
+    assert abs(p["value"] * p["ms_per_step"] - 1e3) <= 5e-5 * p["value"] + 5e-4 * p["ms_per_step"] + 1e-6  # (both rounded)
+    assert {k: p[k] for k in ("metric", "unit", "higher_is_better", "dtype")} == {k: d[k] for k in ("metric", "unit", "higher_is_better", "dtype")}
+    assert not {"roofline", "cpu_baseline", "train_step", "exchange_path"} & set(p)
+    dumped = sorted(os.listdir(full_dir))
+    assert dumped == sorted(os.listdir(plain_dir)) and {"render.npy", "radii.npy", "grad_xyz.npy", "grad_features_rest.npy"} <= set(dumped)
+    for f in dumped:
+        a, b = np.load(os.path.join(plain_dir, f)), np.load(os.path.join(full_dir, f))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, f
+        U.assert_close(a, b, "bench --dump-outputs " + f)
+    assert np.load(os.path.join(plain_dir, "grad_xyz.npy")).shape == (4000, 3) and np.abs(np.load(os.path.join(plain_dir, "render.npy"))).max() > 0
     env["RIGGS_BENCH_BACKEND"] = "gloo"
     import socket
 
@@ -496,14 +514,15 @@ def test_bench_contract_single_and_two_ranks():
             sk.bind(("127.0.0.1", 0))
             return str(sk.getsockname()[1])
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", free_port(), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1"],
+                        "127.0.0.1", "--master-port", free_port(), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d2 = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
     assert d2["n_gpus"] == 2 and d2["config"]["parallelism"] == "frames x2" and "cpu_baseline" not in d2
     assert abs(d2["value"] - 2 * 4 / (d2["ms_per_step"] * 4 / 1e3)) < 1e-3 * d2["value"]  # aggregate over both ranks
-    # the default exchange is the packed-row one (bench.py itself compares it with a plain all-reduce after the timed region)
-    assert d2["config"]["exchange"].startswith("packed rows")
+    # the default exchange is the packed-row one; with --full, bench.py compares it with a plain all-reduce after the timed
+    # region on both ranks (a difference exits non-zero)
+    assert d2["config"]["exchange"].startswith("packed rows") and d2["rows_exchange_verified"] is True
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", free_port(), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1",
                         "--exchange", "dense"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
@@ -518,6 +537,62 @@ def test_bench_contract_single_and_two_ranks():
     assert r.returncode == 0, r.stderr[-2000:]
     d4 = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
     assert d4["n_gpus"] == 2 and d4["steps"] == 3 and d4["config"]["parallelism"] == "frames x2" and d4["value"] > 0
+
+
+def test_bench_dump_outputs_are_what_the_timed_step_returns(tmp_path):
+    """bench.py --dump-outputs on a scene with more Gaussians than bench.DUMP_ROWS: the per-Gaussian arrays are the seeded
+    sample of rows, and every dumped array is what the same frame, issued eagerly here from the same seeded inputs, returns
+    (the eager frame is compared with the CPU oracle by the tests above)."""
+    import os
+    import subprocess
+    import sys
+    import bench
+    from riggs_amd.rasterizer import RasterArena
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    N, J, H, W = bench.DUMP_ROWS + 4001, 8, 96, 112
+    env = dict(os.environ, RIGGS_BENCH_TEST_WORKLOAD="%d,%d,%d,%d" % (N, J, H, W))
+    out_dir = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dump-outputs", out_dir], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    dumped = {f[:-len(".npy")]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+    old = dict(bench.WORKLOAD)
+    bench.WORKLOAD.update(N=N, J=J, H=H, W=W)
+    try:
+        seed = bench.WORKLOAD["seed"]
+        sc, cam, gm, sw = bench.build_workload(0, "cuda:0")
+        # bench.py's dL/dimage: the sign of (first render - seeded target)
+        target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(seed + 100)).cuda()
+        gimg = torch.zeros(3, H, W, device="cuda")
+        step = bench.make_step(cam, gm, sw, gimg, RasterArena(), 1, None)
+        pkg = step()
+        gimg.copy_(torch.sign(pkg["render"].detach() - target) / (3 * H * W))
+        pkg = step()
+        torch.cuda.synchronize()
+    finally:
+        bench.WORKLOAD.clear()
+        bench.WORKLOAD.update(old)
+    want = {k: pkg[k] for k in ("render", "depth", "alpha", "radii")}
+    want["viewspace_points_grad"] = pkg["viewspace_points"].grad
+    for k, p in zip(("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"), gm.parameters()):
+        want["grad_" + k] = p.grad
+    want["grad_node_radius"] = sw._node_radius.grad
+    for k, p in sw.pose_net.named_parameters():
+        want["grad_pose_net." + k] = p.grad
+    assert set(dumped) == set(want)
+    rows = torch.randperm(N, generator=torch.Generator().manual_seed(seed))[:bench.DUMP_ROWS].sort().values
+    assert len(set(rows.tolist())) == bench.DUMP_ROWS
+    for k, v in want.items():
+        v = v.detach().cpu()
+        if v.shape[0] == N:
+            v = v[rows]
+        a = dumped[k]
+        assert a.dtype == (np.float32 if v.is_floating_point() else np.float64) and a.shape == tuple(v.shape), k
+        if k == "radii":
+            np.testing.assert_array_equal(a, v.numpy())
+        else:
+            U.assert_close(a, v.numpy(), "bench --dump-outputs " + k)
+    assert dumped["grad_xyz"].shape == (bench.DUMP_ROWS, 3) and np.abs(dumped["grad_xyz"]).max() > 0 and (dumped["radii"] > 0).any()
 
 
 def test_dist_knn3_at_initialisation_size():

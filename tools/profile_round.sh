@@ -7,7 +7,7 @@ L=${1:-prof}
 O=$PWD/gpurun_out/$L
 mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --metric-only"
+B="python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --metric-only"
 rocprofv3 --kernel-trace --stats -f csv rocpd -d $O/trace -o t -- $B > $O/trace.log 2>&1
 DB=$(find $O/trace -name "*_results.db" | head -1)
 python tools/rocpd_stats.py $DB $O/kernel_stats.csv > $O/kernel_stats.log 2>&1 || true
