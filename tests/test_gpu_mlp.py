@@ -6,6 +6,8 @@ by a power of two on the device) the outputs are within 4e-4 .. 1.5e-3 of the fp
 5 % over all parameters (1-6.5 % per tensor, first layers worst); with bf16 (8 bits) it is 3e-3 .. 1e-2 and 4-19 %.  The sharper test of the kernels
 themselves: agreement with a torch emulation that applies the SAME roundings (identical ReLU masks up to a handful of
 elements in millions)."""
+import ctypes as C
+
 import pytest
 import torch
 
@@ -13,6 +15,8 @@ pytestmark = pytest.mark.gpu
 
 from riggs_amd import mlp as M  # noqa: E402
 from riggs_amd.skeleton import DeformMLP, WeightMLP, _embed  # noqa: E402
+from tests import gpu_util as GU  # noqa: E402
+from tests import mlp_ref as R  # noqa: E402
 
 
 def _rel(a, b):
@@ -547,3 +551,263 @@ def test_fused_head_with_the_folds_equals_the_composition(sparse):
             assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max()) + 1e-30, (name, sparse, n_)
         for q in net.parameters():
             q.grad = None
+
+
+# ---- per element against float64 (tests/mlp_ref.py): every product of the heads' kernels — the data-gradient pass, its bias
+# sums, the forward's hidden layers and output layer, the constant-tail biases — against float64 products of the SAME 16-bit
+# operands, with the rigorous bound of its fp32 accumulation and final rounding; the worst err / bound of every tensor goes to
+# tests.gpu_util.STATS (dumped by tests/conftest.py at the end of a -m gpu run)
+def _head_forms(N, fmt):
+    """The three heads of the per-element tests: (name, net, head, packed weights, the 16-bit embedding operand, pose or None) for the
+    WeightMLP (63 -> 64 input columns, 23 outputs), the DeformMLP in generic form (123 -> 128, 3 outputs, head x 2000) and the
+    DeformMLP with its pose as a constant tail (27 -> 64 per-row columns, the pose through the biases in fp32)."""
+    forms = []
+    nets = _nets(N)
+    for name, net, head, xe in nets:
+        pk = M.FusedHead(net.linear, head, xe.shape[1], net.skips[0], fmt)._packed()
+        forms.append((name, net, head, pk, M.embed_bf16(pk, xe), None))
+    name, net, head, xe = nets[1]
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    x = torch.randn(N, 3, device="cuda", generator=gen) * 0.5
+    pose = torch.randn(96, device="cuda", generator=gen)
+    pk = M.FusedHead(net.linear, head, xe.shape[1] - 96, net.skips[0], fmt, tail_ch=96)._packed()
+    pk.set_tail(pose)
+    forms.append(("DeformMLP-tail", net, head, pk, M.embed_positions_bf16(x, net.multires, fmt=fmt), pose))
+    return forms
+
+
+def _check_forward(tag, net, head, pk, xb, pose, acts, out, rows):
+    """Every hidden layer's stored activations and the fp32 output of the rows ``rows`` (a slice) against float64 of the kernel's
+    own stored inputs: relu(a16 @ W16^T + b [+ W_tail pose]) and acts[D-1]16 @ W_out16^T + b_out.  Returns the output reference
+    and its bound (the sigmoid epilogue's check)."""
+    ic, tc = pk.in_ch, pk.tail_ch
+    x16 = xb[rows][:, :ic]
+    for l in range(pk.depth):
+        W = net.linear[l].weight.detach()
+        wt = W[:, ic:ic + tc] if (tc and (l == 0 or l == pk.skip + 1)) else None
+        if l == 0:
+            a, w = x16, W[:, :ic]
+        elif l == pk.skip + 1:
+            a, w = torch.cat([x16, acts[l - 1, rows]], 1), torch.cat([W[:, :ic], W[:, ic + tc:]], 1)
+        else:
+            a, w = acts[l - 1, rows], W
+        pre, s = R.product(a, w.to(pk.dtype), net.linear[l].bias.detach())
+        extra = 0.0
+        if wt is not None:  # the tail's fp32 columns times the fp32 pose, unrounded, as mlp_tail_bias_kernel reads them
+            t_abs = wt.double().abs() @ pose.double().abs()
+            pre, s = pre + wt.double() @ pose.double(), s + t_abs
+            extra = tc * R.EPS32 * t_abs
+        ref = torch.relu(pre)
+        R.assert_within("mlp acts %s l%d" % (tag, l), acts[l, rows], ref, R.bound(ref, s, a.shape[1] + 1, pk.dtype, extra), stats=GU.STATS)
+    ref, s = R.product(acts[pk.depth - 1, rows], head.weight.detach().to(pk.dtype), head.bias.detach())
+    bnd = R.bound(ref, s, 256 + 1)
+    R.assert_within("mlp out %s" % tag, out[rows], ref, bnd, stats=GU.STATS)
+    return ref, bnd
+
+
+def _check_dgrad(tag, net, head, pk, g16, acts, dpre, rows):
+    """Every layer's data gradient of the rows ``rows`` against float64: the top layer mask (.) (g16 @ W_out16), below it
+    mask_l (.) (dpre_{l+1} @ W16_{l+1}[:, hidden part]) of the kernel's own stored dpre_{l+1}; the mask as tests/mlp_ref.py reads
+    it from the stored activations."""
+    for l in range(pk.depth - 1, -1, -1):
+        if l == pk.depth - 1:
+            u, s = R.product(g16[rows], head.weight.detach().to(pk.dtype).t())
+            k = 32
+        else:
+            W = net.linear[l + 1].weight.detach()
+            u, s = R.product(dpre[l + 1, rows], W[:, W.shape[1] - 256:].to(pk.dtype).t())
+            k = 256
+        must, may = R.relu_mask_rule(acts[l, rows], pk.dtype)
+        R.assert_within("mlp dpre %s l%d" % (tag, l), dpre[l, rows], u, R.bound(u, s, k, pk.dtype), must, may, stats=GU.STATS)
+
+
+def _cotangent16(g, sc, dtype):
+    return (g if sc is None else g * sc).to(dtype)
+
+
+@pytest.mark.parametrize("fmt,gscale", [("fp16", 1.0), ("fp16", 3e-8), ("bf16", 1.0)])
+@pytest.mark.parametrize("N", [1, 31, 32, 33, 127, 128, 129, 255, 257, 4_097, 50_003, 300_000])
+def test_data_gradient_forward_and_bias_sums_per_element_vs_float64(N, fmt, gscale):
+    """riggs_mlp_backward (mlp_backward_kernel) per layer and per element, every row — the ragged last workgroup's included —
+    within the float64 bound; finite everywhere (the DeformMLP's head x 2000 under a scale that lifts max|g| to ~2^10 must not leave
+    fp16's range in an inner layer); the ReLU-mask record equal to (act != 0); the bias sums within the bound of their fp32 sums
+    of the kernel's own dpre; the forward's hidden layers, fp32 output and sigmoid epilogue within theirs; 300 000 = the bench's
+    row count."""
+    for name, net, head, pk, xb, pose in _head_forms(N, fmt):
+        tag = "%s %s g%.0e N=%d" % (name, fmt, gscale, N)
+        out, (acts, masks) = M.forward(pk, xb[:N], True, xb)
+        assert torch.equal(R.decode_masks(masks, N), acts != 0), tag
+        rows = slice(0, N)
+        oref, obnd = _check_forward(tag, net, head, pk, xb, pose, acts, out, rows)
+        sig, _ = M.forward(pk, xb[:N], False, xb, sigmoid=True)
+        sref = torch.sigmoid(oref)
+        R.assert_within("mlp sigmoid %s" % tag, sig, sref, 0.25 * obnd + 8 * R.EPS32 * sref, stats=GU.STATS)
+        gen = torch.Generator(device="cuda").manual_seed(N + 17)
+        g = torch.randn(N, pk.out_ch, device="cuda", generator=gen) * gscale
+        sc = M.grad_scale(g) if fmt == "fp16" else None
+        dpre, db = M.backward_data(pk, g, masks, sc, bias_sums=True)
+        assert bool(torch.isfinite(dpre.float()).all()), tag
+        _check_dgrad(tag, net, head, pk, _cotangent16(g, sc, pk.dtype), acts, dpre, rows)
+        # bias sums: a workgroup's 128 rows in order (fp32) — bitwise the same sequential fp32 sum of its dpre rows (the launch
+        # again into buffers of the test's own: the per-workgroup slices, and the same dpre bits) — then the sum over the
+        # workgroups: 128 + workgroups terms deep against float64
+        from riggs_amd import _lib as L
+        wgs = (N + 127) // 128
+        dpre2 = torch.empty_like(dpre)
+        dbp = torch.full((wgs, pk.depth, 256), float("nan"), device="cuda")
+        L.check(L.lib().riggs_mlp_backward(N, pk.out_ch, pk.depth, pk.skip, pk._wtp, pk.w_out_t_bf16.data_ptr(), g.data_ptr(), L.ptr(sc),
+                                           masks.data_ptr(), dpre2.data_ptr(), dbp.data_ptr(), None, pk.fp16, L.stream_ptr()),
+                "riggs_mlp_backward")
+        assert torch.equal(dpre2.view(torch.int16), dpre.view(torch.int16)), tag
+        rows_f = torch.zeros(pk.depth, wgs * 128, 256, device="cuda")
+        rows_f[:, :N] = dpre.float()
+        rows_f = rows_f.view(pk.depth, wgs, 128, 256)
+        seq = torch.zeros(pk.depth, wgs, 256, device="cuda")
+        for r in range(128):
+            seq = seq + rows_f[:, :, r]
+        assert torch.equal(dbp, seq.transpose(0, 1)), tag
+        d64 = dpre.double()
+        k = 128 + (N + 127) // 128
+        R.assert_within("mlp bias sums %s" % tag, db, d64.sum(1), R.bound(None, d64.abs().sum(1), k), stats=GU.STATS)
+
+
+@pytest.mark.parametrize("fmt", ["fp16", "bf16"])
+@pytest.mark.parametrize("N,frac", [(300_000, 0.07), (300_000, 0.3), (20_011, 1.0), (257, 0.0)])
+def test_row_sparse_rows_are_bitwise_the_dense_rows(N, frac, fmt):
+    """The row-sparse backward's pieces on the compacted rows — live_rows, the repeated forward with the device count, the data
+    gradient with it — against the dense pass: every live row's activations and data gradient are BITWISE the dense row at its index
+    (each element of an MFMA product depends on its own column alone), and the parameter gradients of the sparse path are the float64
+    products over the live rows (the 2e-5 bar of the dense weight-gradient test)."""
+    for name, net, head, xe in _nets(N):
+        pk = M.FusedHead(net.linear, head, xe.shape[1], net.skips[0], fmt)._packed()
+        xb = M.embed_bf16(pk, xe)
+        g = _sparse_cotangent(N, pk.out_ch, frac, mag=3e-8 if fmt == "fp16" else 1.0)
+        sc = M.grad_scale(g) if fmt == "fp16" else None
+        _o, (acts_d, masks_d) = M.forward(pk, xe, True, xb)
+        dpre_d, _ = M.backward_data(pk, g, masks_d, sc, bias_sums=False)
+        idx, count, xl, gl = M.live_rows(pk, g, xb)
+        m = int(count)
+        assert m == int((g != 0).any(1).sum())
+        _o, (acts_s, masks_s) = M.forward(pk, xl[:N], True, xl, n_dev=count)
+        dpre_s, _ = M.backward_data(pk, gl, masks_s, sc, bias_sums=False, n_dev=count)
+        live = idx[:m].long()
+        bits = lambda t: t.view(torch.int16)  # noqa: E731
+        assert torch.equal(bits(acts_s[:, :m]), bits(acts_d[:, live])), (name, fmt, N, frac, "acts")
+        assert torch.equal(bits(dpre_s[:, :m]), bits(dpre_d[:, live])), (name, fmt, N, frac, "dpre")
+        got = M.param_grads(pk, xl, acts_s, dpre_s, gl, sc, n_dev=count)
+        inv = 1.0 if sc is None else 1.0 / float(sc)
+        x64 = xl[:m, :pk.in_ch].double()
+        want = []
+        for l in range(pk.depth):
+            d64 = dpre_s[l, :m].double()
+            a64 = x64 if l == 0 else acts_s[l - 1, :m].double()
+            if l == pk.skip + 1:
+                a64 = torch.cat([x64, a64], 1)
+            want += [d64.t() @ a64 * inv, d64.sum(0) * inv]
+        gob = _cotangent16(gl[:m], sc, pk.dtype).double()
+        want += [gob.t() @ acts_s[pk.depth - 1, :m].double() * inv, gob.sum(0) * inv]
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert a.shape == b.shape, (name, i)
+            tol = 2e-5 * float(b.abs().max()) + 1e-30
+            assert float((a.double() - b).abs().max()) <= tol, (name, fmt, N, frac, i, float((a.double() - b).abs().max()), tol)
+
+
+@pytest.mark.parametrize("fmt", ["fp16", "bf16"])
+def test_rows_past_the_device_count_are_never_read(fmt):
+    """riggs_mlp_forward / riggs_mlp_backward / riggs_mlp_wgrad with a device row count, on buffers whose rows at or past the count —
+    in the operand, the activations, the data gradient, the cotangent — hold NaN: every result equals, bitwise, the one from
+    zero-filled rows, and the output rows past the count are left as they were; count 0, a count inside a workgroup and one past N
+    (clamped)."""
+    from riggs_amd import _lib as L
+    N = 1_000
+    name, net, head, xe = _nets(N)[1]
+    pk = M.FusedHead(net.linear, head, xe.shape[1], net.skips[0], fmt)._packed()
+    xb0 = M.embed_bf16(pk, xe)
+    D, wgs, dev = pk.depth, (N + 127) // 128, "cuda"
+    lib = L.lib()
+    gen = torch.Generator(device=dev).manual_seed(9)
+    g0 = torch.randn(N, pk.out_ch, device=dev, generator=gen) * (3e-8 if fmt == "fp16" else 1.0)
+    sc = M.grad_scale(g0) if fmt == "fp16" else None
+    k_true = [pk.in_ch if l == 0 else (pk.in_ch + 256 if l == pk.skip + 1 else 256) for l in range(D)]
+    nbytes = int(lib.riggs_mlp_wgrad_workspace_bytes(N, pk.in_ch, D, pk.skip))
+    bits = lambda t: t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)  # noqa: E731
+    for count in (0, 1, 300, 777, N, 2_000):
+        c = min(count, N)
+        cw = (c + 127) // 128  # workgroups that hold a row below the count
+        n_dev = torch.full((1,), count, dtype=torch.int32, device=dev)
+        res = {}
+        for fill in (0.0, float("nan")):
+            xb = xb0.clone()
+            xb[c:] = fill
+            acts = torch.full((D, N, 256), fill, dtype=pk.dtype, device=dev)
+            masks = torch.full((D, wgs, 256, 4), 0 if fill == 0 else -1, dtype=torch.int32, device=dev)
+            out = torch.full((N, pk.out_ch), fill, device=dev)
+            L.check(lib.riggs_mlp_forward(N, pk.in_ch, pk.out_ch, D, pk.skip, pk._wp, pk._bp, pk.w_out.data_ptr(), pk.b_out.data_ptr(),
+                                          xb.data_ptr(), acts.data_ptr(), masks.data_ptr(), out.data_ptr(), n_dev.data_ptr(), None,
+                                          pk.fp16, L.stream_ptr()), "riggs_mlp_forward")
+            g = g0.clone()
+            g[c:] = fill
+            dpre = torch.full((D, N, 256), fill, dtype=pk.dtype, device=dev)
+            dbp = torch.full((wgs, D, 256), fill, device=dev)
+            L.check(lib.riggs_mlp_backward(N, pk.out_ch, D, pk.skip, pk._wtp, pk.w_out_t_bf16.data_ptr(), g.data_ptr(), L.ptr(sc),
+                                           masks.data_ptr(), dpre.data_ptr(), dbp.data_ptr(), n_dev.data_ptr(), pk.fp16, L.stream_ptr()),
+                    "riggs_mlp_backward")
+            # the weight gradients read the operand, the activations, the data gradient and the cotangent: NaN past the count in all
+            # four (and a workspace full of NaN: it must initialise what it reads)
+            dpre_w = dpre.clone()
+            acts_w = acts.clone()
+            dpre_w[:, c:] = fill
+            acts_w[:, c:] = fill
+            ws = torch.full((nbytes,), 0 if fill == 0 else 0xFF, dtype=torch.uint8, device=dev)
+            gw = [torch.full((256, k), fill, device=dev) for k in k_true]
+            gb = torch.full((D, 256), fill, device=dev)
+            gwo, gbo = torch.full((pk.out_ch, 256), fill, device=dev), torch.full((pk.out_ch,), fill, device=dev)
+            gwp = (C.c_void_p * D)(*[t.data_ptr() for t in gw])
+            gbp = (C.c_void_p * D)(*[gb[l].data_ptr() for l in range(D)])
+            L.check(lib.riggs_mlp_wgrad(N, pk.in_ch, pk.out_ch, D, pk.skip, xb.data_ptr(), acts_w.data_ptr(), dpre_w.data_ptr(), g.data_ptr(),
+                                        L.ptr(sc), ws.data_ptr(), nbytes, gwp, gbp, gwo.data_ptr(), gbo.data_ptr(), n_dev.data_ptr(),
+                                        pk.fp16, L.stream_ptr()), "riggs_mlp_wgrad")
+            res[fill == 0] = dict(acts=acts, masks=masks, out=out, dpre=dpre, dbp=dbp, grads=gw + [gb, gwo, gbo])
+        z, n = res[True], res[False]
+        tag = (fmt, count)
+        assert torch.equal(bits(z["acts"][:, :c]), bits(n["acts"][:, :c])), tag
+        assert torch.equal(bits(z["out"][:c]), bits(n["out"][:c])), tag
+        assert torch.equal(R.decode_masks(z["masks"], c), R.decode_masks(n["masks"], c)), tag
+        assert torch.equal(bits(z["dpre"][:, :c]), bits(n["dpre"][:, :c])), tag
+        assert torch.equal(bits(z["dbp"][:cw]), bits(n["dbp"][:cw])), tag
+        for a, b in zip(z["grads"], n["grads"]):
+            assert torch.equal(bits(a), bits(b)), tag
+            if c == 0:
+                assert float(a.abs().max()) == 0.0, tag
+        # what lies past the count is left as it was: zeros stay zeros, NaN stays NaN, the untouched workgroups' mask words too
+        for key in ("acts", "dpre"):
+            assert float(z[key][:, c:].float().abs().max() if c < N else 0.0) == 0.0, (tag, key)
+            assert bool(torch.isnan(n[key][:, c:].float()).all()), (tag, key)
+        assert bool(torch.isnan(n["out"][c:]).all()) and bool(torch.isnan(n["dbp"][cw:]).all()), tag
+        assert bool((n["masks"][:, cw:] == -1).all()) and bool((z["masks"][:, cw:] == 0).all()), tag
+
+
+def test_byte_offsets_past_2_31_per_element():
+    """The DeformMLP at N = 600 000: the activations and the data gradient are 8 x N x 512 B = 2.5 GB each, so layers 6 and 7 lie
+    past the 2^31-byte point of both buffers (layer 6 crosses it at row 594 304).  The forward's activations, its output and the
+    data gradient per element against float64 (computed on the device, chunk by chunk), every row."""
+    N, fmt = 600_000, "fp16"
+    name, net, head, xe = _nets(N)[1]
+    pk = M.FusedHead(net.linear, head, xe.shape[1], net.skips[0], fmt)._packed()
+    xb = M.embed_bf16(pk, xe)
+    out, (acts, masks) = M.forward(pk, xe, True, xb)
+    gen = torch.Generator(device="cuda").manual_seed(23)
+    g = torch.randn(N, pk.out_ch, device="cuda", generator=gen) * 3e-8
+    sc = M.grad_scale(g)
+    dpre, _ = M.backward_data(pk, g, masks, sc, bias_sums=False)
+    cross = (1 << 31) // 512 - 6 * N
+    assert 0 < cross < N and acts.stride(0) * 6 + cross * 256 == 1 << 30  # (in 16-bit elements: 2^31 bytes)
+    g16 = _cotangent16(g, sc, pk.dtype)
+    chunk = 65_536
+    starts = sorted(set(list(range(0, N, chunk)) + [cross - chunk // 2]))
+    for r0 in starts:
+        rows = slice(r0, min(N, r0 + chunk))
+        tag = "%s %s N=%d rows %d.." % (name, fmt, N, r0)
+        _check_forward(tag, net, head, pk, xb, None, acts, out, rows)
+        _check_dgrad(tag, net, head, pk, g16, acts, dpre, rows)
+    assert bool(torch.isfinite(dpre.float()).all()) and bool(torch.isfinite(acts.float()).all())
