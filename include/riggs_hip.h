@@ -229,7 +229,8 @@ size_t riggs_raster_backward_workspace_bytes_ordered(int32_t num_points, int64_t
  *   quaternion_to_matrix      utils/time_utils.py:115-132
  *   chain_product_transform   skeleton_utils/skeleton_warp.py:242-273
  *   matrix_to_quaternion      utils/time_utils.py:146-205 (on the detached global rotations)
- * local_rot (J,4) un-normalised wxyz; joints (J,3); parents (J,) int32 with parents[i] < i.
+ * local_rot (J,4) un-normalised wxyz; joints (J,3); parents (J,) int32 with parents[i] < i; 1 <= J <= 256 (J <= 64: one
+ * wave64, 65..256: one 256-thread workgroup, a barrier per tree level).
  * Outputs: transforms (J,12) = rows of [R|t] 3x4, node_rot (J,4), d_nodes (J,3) = posed + global_trans. */
 int riggs_fk_forward(int32_t num_joints, const float* local_rot, const float* joints, const int32_t* parents,
                      const float* global_trans, float* transforms, float* node_rot, float* d_nodes,
@@ -246,7 +247,8 @@ int riggs_fk_backward(int32_t num_joints, const float* local_rot, const float* j
  *   LBS of means / quaternion     skeleton_warp.py:149-165
  * x (N,3), motion_mask (N,) or NULL (= ones), node_radius_log (J,) = SkeletonWarp._node_radius.
  * Outputs d_xyz (N,3), d_rotation (N,4); optional nn_weight (N,Kp) / nn_idx (N,Kp) int64 where
- * Kp = J-1 (K<=0) or K — needed by render_rig.py:156-158, not by training (may be NULL). */
+ * Kp = J-1 (K<=0) or K — needed by render_rig.py:156-158, not by training (may be NULL).  2 <= J <= 256 (J > 64: kernels of
+ * their own with up to 255 bone records in LDS; riggs_lbs_forward_fk then runs the chain as a launch in front). */
 int riggs_lbs_forward(int32_t num_points, int32_t num_joints, int32_t K, const float* x, const float* joints,
                       const int32_t* parents, const float* node_radius_log, const float* transforms,
                       const float* node_rot, const float* global_trans, const float* motion_mask,
@@ -258,7 +260,8 @@ int riggs_lbs_forward(int32_t num_points, int32_t num_joints, int32_t K, const f
  * it the all-bones forward (K = -1, no weight_mod, no nn outputs) of a LARGE scene (>= 1 M Gaussians, >= 16 joints) reads the bone
  * records through the scalar cache as SGPR operands — a one-workgroup launch writes the table (and, in the _fk form, runs the
  * chain) in front — instead of staging them in every workgroup's LDS: 2 M x 64 joints 129 -> 104 us, results bit-identical.
- * riggs_set_option("lbs_scalar", 1 / -1) forces / forbids the form at every size (default 0: by size). */
+ * riggs_set_option("lbs_scalar", 1 / -1) forces / forbids the form at every size (default 0: by size).  A <= 64-joint form: the
+ * table holds 64 records, and skeletons of more joints never read it. */
 size_t riggs_lbs_bone_table_bytes(void);
 /* The same with the forward kinematics INSIDE the launch (every workgroup runs the chain of J - 1 dependent 3x4 products
  * itself — 2 us — instead of a launch of its own in front — 6.5 us of a captured frame): takes the pose, and workgroup 0

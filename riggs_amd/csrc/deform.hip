@@ -1,8 +1,8 @@
 // Skeleton-driven deformation of the Gaussian cloud:
-//   fk_*   : forward kinematics over <= 64 joints on ONE wave64 (replaces ~3*J torch launches
-//            of SkeletonWarp.chain_product_transform, skeleton_warp.py:242-273)
+//   fk_*   : forward kinematics over <= 64 joints on ONE wave64, <= 256 on one workgroup (replaces ~3*J torch
+//            launches of SkeletonWarp.chain_product_transform, skeleton_warp.py:242-273)
 //   lbs_*  : bone-distance skinning weights + linear blend skinning fused per Gaussian, with the
-//            <= 63 bone records (segment, radius, 3x4 transform, quaternion) staged in LDS.
+//            <= 63 (<= 255: the *_wide kernels) bone records (segment, radius, 3x4 transform, quaternion) staged in LDS.
 // Backward reduces over the N Gaussians inside the kernel: wave64 DPP sums -> LDS -> one atomic
 // per workgroup per output.
 #include "fk_device.h"
@@ -749,6 +749,422 @@ static void launch_lbs_bwd_bonelane(const LbsArgs& a, hipStream_t s) {
   else launch_lbs_bwd_bonelane_g<NBLK, LB_GPB>(a, s);
 }
 
+// ==================================================================================== skeletons of 65..256 joints
+// Separate kernels, so the <= 64-joint ones keep their LDS footprint, registers and occupancy: the chain on one workgroup
+// (fk_device.h: fk_block_*), up to 255 bone records in LDS, the top-K selection mask as 256 bits per thread in LDS, and the
+// bone-lane backward walking the bones in passes of 64.
+#define MAX_B_WIDE (MAX_J_WIDE - 1)
+
+__global__ __launch_bounds__(256) void fk_forward_wide_kernel(int J, const float* __restrict__ local_rot,
+                                                              const float* __restrict__ joints,
+                                                              const int32_t* __restrict__ parents,
+                                                              const float* __restrict__ global_trans,
+                                                              float* __restrict__ transforms, float* __restrict__ node_rot,
+                                                              float* __restrict__ d_nodes) {
+  __shared__ FkWideShared sh;
+  const int j = threadIdx.x;
+  FkIn in;
+  fk_load_joint(j, J, local_rot, joints, parents, nullptr, nullptr, in, nullptr);
+  FkWide f;
+  fk_block_forward(J, in, f, sh);
+  if (j < J) {
+    float G[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) G[e] = sh.G[j][e];
+    const float x = in.x[0], y = in.x[1], z = in.x[2];
+#pragma unroll
+    for (int e = 0; e < 12; e++) transforms[12 * j + e] = G[e];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+      d_nodes[3 * j + r] = (G[4 * r] * x + G[4 * r + 1] * y + G[4 * r + 2] * z + G[4 * r + 3]) + global_trans[r];
+    float q[4];
+    R_to_quat(G, q);
+#pragma unroll
+    for (int e = 0; e < 4; e++) node_rot[4 * j + e] = q[e];
+  }
+}
+
+__global__ __launch_bounds__(256) void fk_backward_wide_kernel(int J, const float* __restrict__ local_rot,
+                                                               const float* __restrict__ joints,
+                                                               const int32_t* __restrict__ parents,
+                                                               const float* __restrict__ dL_dG_in,
+                                                               const float* __restrict__ dL_dnodes,
+                                                               float* __restrict__ dL_dlocal_rot,
+                                                               float* __restrict__ dL_dglobal_trans) {
+  __shared__ FkWideShared sh;
+  const int j = threadIdx.x;
+  FkIn in;
+  fk_load_joint(j, J, local_rot, joints, parents, dL_dG_in, dL_dnodes, in, nullptr);
+  FkWide f;
+  fk_block_forward(J, in, f, sh);
+  if (dL_dnodes && j < 3) {  // d_nodes = posed + global_trans
+    float s = 0.f;
+    for (int k = 0; k < J; k++) s += dL_dnodes[3 * k + j];
+    dL_dglobal_trans[j] += s;
+  }
+  float dq[4];
+  fk_block_backward(J, in, f, sh, dq);
+  if (j < J) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) dL_dlocal_rot[4 * j + e] = dq[e];
+  }
+}
+
+// topk_mask over up to 255 bones: the same K passes in the same (d2, index) order, the thread's 256-bit mask a column of
+// `sel` in LDS (word w of thread t at sel[w][t]: conflict-free)
+typedef uint32_t SelWide[FK_WIDE_WORDS][256];
+__device__ __forceinline__ void topk_mask_wide(const Bone* bones, int B, int K, float px, float py, float pz, SelWide& sel) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int w = 0; w < FK_WIDE_WORDS; w++) sel[w][t] = 0u;
+  for (int s = 0; s < K; s++) {
+    float best = INFINITY;
+    int bi = -1;
+    uint32_t m = 0u;
+    for (int k = 0; k < B; k++) {
+      if ((k & 31) == 0) m = sel[k >> 5][t];
+      if ((m >> (k & 31)) & 1u) continue;
+      const float d2 = bone_d2(bones[k], px, py, pz);
+      if (d2 < best || bi < 0) { best = d2; bi = k; }
+    }
+    sel[bi >> 5][t] |= 1u << (bi & 31);
+  }
+}
+
+// lbs_forward_kernel<TOPK, false, 1> for J > 64 (riggs_lbs_forward_fk runs the chain as a launch of its own in front)
+template <bool TOPK>
+__global__ __launch_bounds__(256) void lbs_forward_wide_kernel(LbsArgs a) {
+  __shared__ Bone bones[MAX_B_WIDE];
+  __shared__ SelWide s_sel;
+  const int t = threadIdx.x;
+  const int n = blockIdx.x * 256 + t;
+  const bool on = n < a.N;
+  const int nn = min(n, a.N - 1);
+  const float px = a.x[3 * nn], py = a.x[3 * nn + 1], pz = a.x[3 * nn + 2];
+  stage_bones(a, bones);
+  if (!on) return;
+  const int B = a.J - 1;
+  if (TOPK) topk_mask_wide(bones, B, a.K, px, py, pz, s_sel);
+  float M[12], qa[4] = {0.f, 0.f, 0.f, 0.f}, sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 12; e++) M[e] = 0.f;
+  uint32_t m = 0u;
+  for (int k = 0; k < B; k++) {
+    if (TOPK) {
+      if ((k & 31) == 0) m = s_sel[k >> 5][t];
+      if (!((m >> (k & 31)) & 1u)) continue;
+    }
+    const Bone& b = bones[k];
+    const float d2 = TOPK ? bone_d2(b, px, py, pz) : bone_d2_fast(b, px, py, pz);
+    float u = fast_exp(-d2 * b.inv2r2);                            // skeleton_warp.py:66
+    if (a.weight_mod) u *= a.weight_mod[(size_t)n * B + k];        // :68-69
+    const float v = u + 1e-7f;                                     // :71
+    sum += v;
+#pragma unroll
+    for (int e = 0; e < 12; e++) M[e] += v * b.G[e];
+#pragma unroll
+    for (int e = 0; e < 4; e++) qa[e] += v * b.q[e];
+  }
+  const float gx = a.global_trans[0], gy = a.global_trans[1], gz = a.global_trans[2];
+  const float inv = 1.0f / sum;
+  const float mm = a.motion_mask ? a.motion_mask[n] : 1.0f;
+  const float ax = (M[0] * px + M[1] * py + M[2] * pz + M[3]) * inv + gx;
+  const float ay = (M[4] * px + M[5] * py + M[6] * pz + M[7]) * inv + gy;
+  const float az = (M[8] * px + M[9] * py + M[10] * pz + M[11]) * inv + gz;
+  a.d_xyz[3 * n] = (ax - px) * mm; a.d_xyz[3 * n + 1] = (ay - py) * mm; a.d_xyz[3 * n + 2] = (az - pz) * mm;
+  reinterpret_cast<float4*>(a.d_rot)[n] = make_float4(qa[0] * inv * mm, qa[1] * inv * mm, qa[2] * inv * mm, qa[3] * inv * mm);
+  if (!a.nn_weight && !a.nn_idx) return;
+  if (TOPK) {
+    // ascending-d2 order like torch.topk(largest=False): K selection passes inside the mask (cleared as they go)
+    for (int s = 0; s < a.K; s++) {
+      float best = INFINITY; int bi = -1;
+      for (int k = 0; k < B; k++) {
+        if ((k & 31) == 0) m = s_sel[k >> 5][t];
+        if (!((m >> (k & 31)) & 1u)) continue;
+        const float d2 = bone_d2(bones[k], px, py, pz);
+        if (d2 < best || bi < 0) { best = d2; bi = k; }
+      }
+      s_sel[bi >> 5][t] &= ~(1u << (bi & 31));
+      if (a.nn_weight) a.nn_weight[(size_t)n * a.K + s] = (fast_exp(-best * bones[bi].inv2r2) + 1e-7f) * inv;
+      if (a.nn_idx) a.nn_idx[(size_t)n * a.K + s] = bi + 1;
+    }
+  } else {
+    for (int k = 0; k < B; k++) {
+      if (a.nn_weight) a.nn_weight[(size_t)n * B + k] = (fast_exp(-bone_d2_fast(bones[k], px, py, pz) * bones[k].inv2r2) *
+                                                            (a.weight_mod ? a.weight_mod[(size_t)n * B + k] : 1.0f) + 1e-7f) * inv;
+      if (a.nn_idx) a.nn_idx[(size_t)n * B + k] = k + 1;
+    }
+  }
+}
+
+// lbs_backward_kernel (top-K, thread per Gaussian) for J > 64
+__global__ __launch_bounds__(256) void lbs_backward_wide_kernel(LbsArgs a) {
+  __shared__ Bone bones[MAX_B_WIDE];
+  __shared__ float s_acc[MAX_B_WIDE][13];
+  __shared__ SelWide s_sel;
+  __shared__ float s_gt[3];
+  stage_bones(a, bones);
+  const int B = a.J - 1, t = threadIdx.x;
+  for (int e = t; e < B * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
+  if (t < 3) s_gt[t] = 0.f;
+  __syncthreads();
+  const int n = blockIdx.x * 256 + t;
+  const bool valid = n < a.N;
+  const int lane = t & 63;
+  float px = 0.f, py = 0.f, pz = 0.f, m = 0.f;
+  float g[3] = {0.f, 0.f, 0.f}, h[4] = {0.f, 0.f, 0.f, 0.f};
+  if (valid) {
+    px = a.x[3 * n]; py = a.x[3 * n + 1]; pz = a.x[3 * n + 2];
+    m = a.motion_mask ? a.motion_mask[n] : 1.0f;
+    g[0] = a.g_xyz[3 * n]; g[1] = a.g_xyz[3 * n + 1]; g[2] = a.g_xyz[3 * n + 2];
+    const float4 hh = reinterpret_cast<const float4*>(a.g_rot)[n];
+    h[0] = hh.x; h[1] = hh.y; h[2] = hh.z; h[3] = hh.w;
+  }
+  const float gh[3] = {g[0] * m, g[1] * m, g[2] * m};
+  const float hh4[4] = {h[0] * m, h[1] * m, h[2] * m, h[3] * m};
+  // pass 1: normaliser and blended outputs
+  topk_mask_wide(bones, B, a.K, px, py, pz, s_sel);
+  float M[12], qa[4] = {0.f, 0.f, 0.f, 0.f}, sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 12; e++) M[e] = 0.f;
+  uint32_t sm = 0u;
+  for (int k = 0; k < B; k++) {
+    if ((k & 31) == 0) sm = s_sel[k >> 5][t];
+    if (!((sm >> (k & 31)) & 1u)) continue;
+    const Bone& b = bones[k];
+    const float d2 = bone_d2(b, px, py, pz);
+    const float v = fast_exp(-d2 * b.inv2r2) + 1e-7f;
+    sum += v;
+#pragma unroll
+    for (int e = 0; e < 12; e++) M[e] += v * b.G[e];
+#pragma unroll
+    for (int e = 0; e < 4; e++) qa[e] += v * b.q[e];
+  }
+  const float inv = valid ? 1.0f / sum : 0.f;
+  const float ax = (M[0] * px + M[1] * py + M[2] * pz + M[3]) * inv;
+  const float ay = (M[4] * px + M[5] * py + M[6] * pz + M[7]) * inv;
+  const float az = (M[8] * px + M[9] * py + M[10] * pz + M[11]) * inv;
+  const float qv[4] = {qa[0] * inv, qa[1] * inv, qa[2] * inv, qa[3] * inv};
+  const float S = gh[0] * ax + gh[1] * ay + gh[2] * az + hh4[0] * qv[0] + hh4[1] * qv[1] + hh4[2] * qv[2] + hh4[3] * qv[3];
+  if (valid && a.dmask) {
+    const float gxs = a.global_trans[0], gys = a.global_trans[1], gzs = a.global_trans[2];
+    a.dmask[n] = g[0] * (ax + gxs - px) + g[1] * (ay + gys - py) + g[2] * (az + gzs - pz) + h[0] * qv[0] + h[1] * qv[1] +
+                 h[2] * qv[2] + h[3] * qv[3];
+  }
+  // pass 2: per-bone contributions, reduced over the wave
+  const float P[12] = {gh[0] * px, gh[0] * py, gh[0] * pz, gh[0], gh[1] * px, gh[1] * py, gh[1] * pz, gh[1],
+                       gh[2] * px, gh[2] * py, gh[2] * pz, gh[2]};
+  for (int k = 0; k < B; k++) {
+    if ((k & 31) == 0) sm = s_sel[k >> 5][t];
+    const Bone& b = bones[k];
+    const float d2 = bone_d2(b, px, py, pz);
+    float w = 0.f, r = 0.f;
+    const bool sel = valid && ((sm >> (k & 31)) & 1u);
+    if (sel) {
+      const float u = fast_exp(-d2 * b.inv2r2);
+      w = (u + 1e-7f) * inv;
+      const float Ax = b.G[0] * px + b.G[1] * py + b.G[2] * pz + b.G[3];
+      const float Ay = b.G[4] * px + b.G[5] * py + b.G[6] * pz + b.G[7];
+      const float Az = b.G[8] * px + b.G[9] * py + b.G[10] * pz + b.G[11];
+      const float dLdw = gh[0] * Ax + gh[1] * Ay + gh[2] * Az + hh4[0] * b.q[0] + hh4[1] * b.q[1] + hh4[2] * b.q[2] + hh4[3] * b.q[3];
+      const float dLdv = (dLdw - S) * inv;
+      r = dLdv * u * d2 * (2.0f * b.inv2r2);
+    }
+    float red[13];
+#pragma unroll
+    for (int e = 0; e < 12; e++) red[e] = wave_sum(w * P[e]);
+    red[12] = wave_sum(r);
+    if (lane == 63) {
+#pragma unroll
+      for (int e = 0; e < 13; e++) atomicAdd(&s_acc[k][e], red[e]);
+    }
+  }
+  const float t0 = wave_sum(gh[0]), t1 = wave_sum(gh[1]), t2 = wave_sum(gh[2]);
+  if (lane == 63) { atomicAdd(&s_gt[0], t0); atomicAdd(&s_gt[1], t1); atomicAdd(&s_gt[2], t2); }
+  __syncthreads();
+  for (int e = t; e < B * 13; e += 256) {
+    const int k = e / 13, c = e % 13;
+    const float v = s_acc[k][c];
+    if (c < 12) atomicAdd(&a.dG[12 * (k + 1) + c], v);
+    else atomicAdd(&a.drho[k + 1], v);
+  }
+  if (t < 3) atomicAdd(&a.dgt[t], s_gt[t]);
+}
+
+// lbs_backward_bonelane_kernel (all bones) for J > 64.  A lane keeps the 13 sums of at most LBW_PASS blocks of 8 bones in
+// registers, so the bones are walked in passes of LBW_PASS blocks.  The per-Gaussian normaliser spans every bone: a first walk
+// over the wave's listed Gaussians computes it (and dL/dmotion_mask) and leaves (1/sum, S) in LDS; each gradient pass then
+// recomputes its bones' terms.  Same per-workgroup partials and finish kernel as the <= 64-joint form.
+#define LBW_NBLK (MAX_J_WIDE / LB_BONES)  // 32 blocks of 8 bones
+#define LBW_PASS 8                         // blocks per gradient pass
+template <bool MOD>
+__global__ __launch_bounds__(256) void lbs_backward_bonelane_wide_kernel(LbsArgs a) {
+  constexpr int GPB = LB_GPB;
+  __shared__ Bone bones[LBW_NBLK * LB_BONES];
+  __shared__ float s_acc[LBW_NBLK * LB_BONES][13];
+  __shared__ float s_gt[3];
+  __shared__ float2 s_norm[4][GPB / 4];
+  __shared__ unsigned short s_list[4][GPB / 4];
+  const int B = a.J - 1;
+  const int nblk = (B + LB_BONES - 1) / LB_BONES;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slot = lane >> 3, bl = lane & 7;
+  const int wave_first = blockIdx.x * GPB + wave * (GPB / 4);
+  const int wave_end = min(a.N, wave_first + GPB / 4);
+  stage_bones(a, bones);
+  for (int k = B + threadIdx.x; k < nblk * LB_BONES; k += 256) {  // padding bones: never selected
+    Bone z;
+    memset(&z, 0, sizeof(z));
+    z.len2c = 1.f;
+    bones[k] = z;
+  }
+  for (int e = threadIdx.x; e < nblk * LB_BONES * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
+  if (threadIdx.x < 3) s_gt[threadIdx.x] = 0.f;
+  __syncthreads();
+  // the wave's Gaussians with an incoming gradient, listed (the others: zeros of the per-Gaussian outputs)
+  int n_work = 0;
+#pragma unroll 1
+  for (int g = 0; g < GPB / 4 / 64; g++) {
+    const int n = wave_first + 64 * g + lane;
+    bool touched = false;
+    if (n < wave_end) {
+      const float4 hq = reinterpret_cast<const float4*>(a.g_rot)[n];
+      touched = (a.g_xyz[3 * n] != 0.f) || (a.g_xyz[3 * n + 1] != 0.f) || (a.g_xyz[3 * n + 2] != 0.f) ||
+                (hq.x != 0.f) || (hq.y != 0.f) || (hq.z != 0.f) || (hq.w != 0.f);
+      if (!touched && a.dmask) a.dmask[n] = 0.f;
+      if (!touched && MOD) {
+        for (int k = 0; k < B; k++) a.dmod[(size_t)n * B + k] = 0.f;
+      }
+    }
+    const uint64_t tm = __builtin_amdgcn_ballot_w64(touched);
+    if (touched) s_list[wave][n_work + __builtin_popcountll(tm & ((1ull << lane) - 1ull))] = (unsigned short)(64 * g + lane);
+    n_work += __builtin_popcountll(tm);
+  }
+  struct StepOps { int n; bool valid; float px, py, pz, m, g0, g1, g2; float4 h; };
+  auto fetch = [&](int w0) {
+    StepOps o;
+    o.valid = w0 + slot < n_work;
+    o.n = o.valid ? wave_first + (int)s_list[wave][w0 + slot] : 0;
+    o.px = 0.f; o.py = 0.f; o.pz = 0.f; o.m = 0.f; o.g0 = 0.f; o.g1 = 0.f; o.g2 = 0.f;
+    o.h = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (o.valid) {
+      o.px = a.x[3 * o.n]; o.py = a.x[3 * o.n + 1]; o.pz = a.x[3 * o.n + 2];
+      o.m = a.motion_mask ? a.motion_mask[o.n] : 1.0f;
+      o.g0 = a.g_xyz[3 * o.n]; o.g1 = a.g_xyz[3 * o.n + 1]; o.g2 = a.g_xyz[3 * o.n + 2];
+      o.h = reinterpret_cast<const float4*>(a.g_rot)[o.n];
+    }
+    return o;
+  };
+  const float gx = a.global_trans[0], gy = a.global_trans[1], gz = a.global_trans[2];
+  // the normaliser over every bone: sum_k v_k and S = sum_k w_k dL/dw_k
+#pragma unroll 1
+  for (int w0 = 0; w0 < n_work; w0 += 8) {
+    const StepOps cu = fetch(w0);
+    const float px = cu.px, py = cu.py, pz = cu.pz, m = cu.m;
+    const float gh0 = cu.g0 * m, gh1 = cu.g1 * m, gh2 = cu.g2 * m;
+    const float hh0 = cu.h.x * m, hh1 = cu.h.y * m, hh2 = cu.h.z * m, hh3 = cu.h.w * m;
+    float sum = 0.f, sv = 0.f, su = 0.f;
+#pragma unroll 2
+    for (int bb = 0; bb < nblk; bb++) {
+      const int k = bb * LB_BONES + bl;
+      const Bone& b = bones[k];
+      const float d2 = bone_d2_fast(b, px, py, pz);
+      const bool on = cu.valid && (k < B);
+      const float u = on ? fast_exp(-d2 * b.inv2r2) : 0.f;
+      float v;
+      if constexpr (MOD) v = on ? u * a.weight_mod[(size_t)cu.n * B + k] + 1e-7f : 0.f;
+      else v = on ? u + 1e-7f : 0.f;
+      const float Ax = b.G[0] * px + b.G[1] * py + b.G[2] * pz + b.G[3];
+      const float Ay = b.G[4] * px + b.G[5] * py + b.G[6] * pz + b.G[7];
+      const float Az = b.G[8] * px + b.G[9] * py + b.G[10] * pz + b.G[11];
+      const float dw = gh0 * Ax + gh1 * Ay + gh2 * Az + hh0 * b.q[0] + hh1 * b.q[1] + hh2 * b.q[2] + hh3 * b.q[3];
+      const float du = cu.g0 * Ax + cu.g1 * Ay + cu.g2 * Az + cu.h.x * b.q[0] + cu.h.y * b.q[1] + cu.h.z * b.q[2] + cu.h.w * b.q[3];
+      sum += v;
+      sv += v * dw;
+      su += v * du;
+    }
+    sum = row8_sum(sum);
+    sv = row8_sum(sv);
+    const float inv = cu.valid ? 1.0f / sum : 0.f;
+    const float S = sv * inv;
+    if (a.dmask) {
+      su = row8_sum(su);
+      if (cu.valid && bl == 0) a.dmask[cu.n] = su * inv + cu.g0 * (gx - px) + cu.g1 * (gy - py) + cu.g2 * (gz - pz);
+    }
+    if (cu.valid && bl == 0) s_norm[wave][w0 + slot] = make_float2(inv, S);
+  }
+  __syncthreads();
+  float gt0 = 0.f, gt1 = 0.f, gt2 = 0.f;
+#pragma unroll 1
+  for (int p0 = 0; p0 < nblk; p0 += LBW_PASS) {
+    float acc[LBW_PASS][13];
+#pragma unroll
+    for (int bb = 0; bb < LBW_PASS; bb++)
+#pragma unroll
+      for (int e = 0; e < 13; e++) acc[bb][e] = 0.f;
+#pragma unroll 1
+    for (int w0 = 0; w0 < n_work; w0 += 8) {
+      const StepOps cu = fetch(w0);
+      const bool valid = cu.valid;
+      const int n = cu.n;
+      const float px = cu.px, py = cu.py, pz = cu.pz, m = cu.m;
+      const float2 nrm = valid ? s_norm[wave][w0 + slot] : make_float2(0.f, 0.f);
+      const float inv = nrm.x, S = nrm.y;
+      const float gh0 = cu.g0 * m, gh1 = cu.g1 * m, gh2 = cu.g2 * m;
+      const float hh0 = cu.h.x * m, hh1 = cu.h.y * m, hh2 = cu.h.z * m, hh3 = cu.h.w * m;
+      const float P[12] = {gh0 * px, gh0 * py, gh0 * pz, gh0, gh1 * px, gh1 * py, gh1 * pz, gh1,
+                           gh2 * px, gh2 * py, gh2 * pz, gh2};
+#pragma unroll
+      for (int bb = 0; bb < LBW_PASS; bb++) {
+        if (p0 + bb >= nblk) break;
+        const int k = (p0 + bb) * LB_BONES + bl;
+        const Bone& b = bones[k];
+        const float d2 = bone_d2_fast(b, px, py, pz);
+        const bool on = valid && (k < B);
+        const float u = on ? fast_exp(-d2 * b.inv2r2) : 0.f;
+        float md = 1.0f, v;
+        if constexpr (MOD) {
+          md = on ? a.weight_mod[(size_t)n * B + k] : 1.0f;
+          v = on ? u * md + 1e-7f : 0.f;
+        } else {
+          v = on ? u + 1e-7f : 0.f;
+        }
+        const float Ax = b.G[0] * px + b.G[1] * py + b.G[2] * pz + b.G[3];
+        const float Ay = b.G[4] * px + b.G[5] * py + b.G[6] * pz + b.G[7];
+        const float Az = b.G[8] * px + b.G[9] * py + b.G[10] * pz + b.G[11];
+        const float dw = gh0 * Ax + gh1 * Ay + gh2 * Az + hh0 * b.q[0] + hh1 * b.q[1] + hh2 * b.q[2] + hh3 * b.q[3];
+        const float w = v * inv;
+        const float dLdv = (dw - S) * inv;
+        float r;
+        if constexpr (MOD) r = dLdv * md * u * d2 * (2.0f * b.inv2r2);
+        else r = dLdv * u * d2 * (2.0f * b.inv2r2);
+        if (MOD && on) a.dmod[(size_t)n * B + k] = dLdv * u;  // v = u * mod + 1e-7
+#pragma unroll
+        for (int e = 0; e < 12; e++) acc[bb][e] += w * P[e];
+        acc[bb][12] += r;
+      }
+      if (p0 == 0 && bl == 0) { gt0 += gh0; gt1 += gh1; gt2 += gh2; }
+    }
+    // fold the 8 slot rows (lanes l, l^8, l^16, l^32) into the workgroup's sums of this pass's bones
+#pragma unroll
+    for (int bb = 0; bb < LBW_PASS; bb++) {
+      if (p0 + bb >= nblk) break;
+#pragma unroll
+      for (int e = 0; e < 13; e++) {
+        float t = acc[bb][e];
+        t += __shfl_xor(t, 8); t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
+        if (slot == 0) atomicAdd(&s_acc[(p0 + bb) * LB_BONES + bl][e], t);
+      }
+    }
+  }
+  gt0 = wave_sum(gt0); gt1 = wave_sum(gt1); gt2 = wave_sum(gt2);
+  if (lane == 63) { atomicAdd(&s_gt[0], gt0); atomicAdd(&s_gt[1], gt1); atomicAdd(&s_gt[2], gt2); }
+  __syncthreads();
+  float* part = a.partial + (size_t)blockIdx.x * (B * 13 + 3);
+  for (int e = threadIdx.x; e < B * 13; e += 256) part[e] = (&s_acc[0][0])[e];
+  if (threadIdx.x < 3) part[B * 13 + threadIdx.x] = s_gt[threadIdx.x];
+}
+
 }  // namespace riggs
 
 using namespace riggs;
@@ -758,11 +1174,13 @@ extern "C" {
 int riggs_fk_forward(int32_t J, const float* local_rot, const float* joints, const int32_t* parents,
                      const float* global_trans, float* transforms, float* node_rot, float* d_nodes,
                      riggs_stream stream) {
-  RIGGS_REQUIRE(J >= 1 && J <= MAX_J, "num_joints must be in [1, 64]");
+  RIGGS_REQUIRE(J >= 1 && J <= MAX_J_WIDE, "num_joints must be in [1, 256]");
   {
     ProfScope ps(PROF_FK_FWD, (hipStream_t)stream);
-    hipLaunchKernelGGL(fk_forward_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, J, local_rot, joints, parents,
-                       global_trans, transforms, node_rot, d_nodes);
+    if (J <= MAX_J) hipLaunchKernelGGL(fk_forward_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, J, local_rot, joints, parents,
+                                       global_trans, transforms, node_rot, d_nodes);
+    else hipLaunchKernelGGL(fk_forward_wide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, J, local_rot, joints, parents,
+                            global_trans, transforms, node_rot, d_nodes);
   }
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
@@ -771,11 +1189,13 @@ int riggs_fk_forward(int32_t J, const float* local_rot, const float* joints, con
 int riggs_fk_backward(int32_t J, const float* local_rot, const float* joints, const int32_t* parents,
                       const float* dL_dtransforms, const float* dL_dd_nodes, float* dL_dlocal_rot,
                       float* dL_dglobal_trans, riggs_stream stream) {
-  RIGGS_REQUIRE(J >= 1 && J <= MAX_J, "num_joints must be in [1, 64]");
+  RIGGS_REQUIRE(J >= 1 && J <= MAX_J_WIDE, "num_joints must be in [1, 256]");
   {
     ProfScope ps(PROF_FK_BWD, (hipStream_t)stream);
-    hipLaunchKernelGGL(fk_backward_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, J, local_rot, joints, parents,
-                       dL_dtransforms, dL_dd_nodes, dL_dlocal_rot, dL_dglobal_trans);
+    if (J <= MAX_J) hipLaunchKernelGGL(fk_backward_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, J, local_rot, joints, parents,
+                                       dL_dtransforms, dL_dd_nodes, dL_dlocal_rot, dL_dglobal_trans);
+    else hipLaunchKernelGGL(fk_backward_wide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, J, local_rot, joints, parents,
+                            dL_dtransforms, dL_dd_nodes, dL_dlocal_rot, dL_dglobal_trans);
   }
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
@@ -784,7 +1204,7 @@ int riggs_fk_backward(int32_t J, const float* local_rot, const float* joints, co
 static int fill_lbs(LbsArgs& a, int32_t N, int32_t J, int32_t K, const float* x, const float* joints,
                     const int32_t* parents, const float* rho, const float* transforms, const float* node_rot,
                     const float* gt, const float* mask) {
-  RIGGS_REQUIRE(J >= 2 && J <= MAX_J, "num_joints must be in [2, 64]");
+  RIGGS_REQUIRE(J >= 2 && J <= MAX_J_WIDE, "num_joints must be in [2, 256]");
   RIGGS_REQUIRE(N >= 0, "num_points < 0");
   RIGGS_REQUIRE(K < J, "K must be < num_joints");
   memset(&a, 0, sizeof(a));
@@ -823,6 +1243,13 @@ int riggs_lbs_forward(int32_t N, int32_t J, int32_t K, const float* x, const flo
   a.weight_mod = weight_mod;
   RIGGS_REQUIRE(weight_mod == nullptr || K <= 0, "weight_mod is supported with K = -1 (all bones) only");
   if (N == 0) return 0;
+  if (J > MAX_J) {  // (the bone table is a <= 64-joint form)
+    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
+    if (a.K > 0) hipLaunchKernelGGL(lbs_forward_wide_kernel<true>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(lbs_forward_wide_kernel<false>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
+    RIGGS_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   if (lbs_use_scalar(a, bone_table) && !nn_weight && !nn_idx) {
     Bone* table = (Bone*)bone_table;
     hipLaunchKernelGGL(lbs_bone_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, table);
@@ -857,6 +1284,17 @@ int riggs_lbs_forward_fk(int32_t N, int32_t J, int32_t K, const float* x, const 
   RIGGS_REQUIRE(weight_mod == nullptr || K <= 0, "weight_mod is supported with K = -1 (all bones) only");
   RIGGS_REQUIRE(local_rot && transforms && node_rot && d_nodes, "riggs_lbs_forward_fk needs the pose and the three chain outputs");
   if (N == 0) return riggs_fk_forward(J, local_rot, joints, parents, global_trans, transforms, node_rot, d_nodes, stream);
+  if (J > MAX_J) {
+    // the wide chain as a launch of its own in front of the skinning: inside every workgroup it would cost each of them the
+    // whole sweep (one barrier per level: a 256-joint chain is 255 levels)
+    rc = riggs_fk_forward(J, local_rot, joints, parents, global_trans, transforms, node_rot, d_nodes, stream);
+    if (rc) return rc;
+    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
+    if (a.K > 0) hipLaunchKernelGGL(lbs_forward_wide_kernel<true>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(lbs_forward_wide_kernel<false>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
+    RIGGS_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   if (lbs_use_scalar(a, bone_table)) {
     Bone* table = (Bone*)bone_table;
     hipLaunchKernelGGL(lbs_fk_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, table);
@@ -910,7 +1348,15 @@ int riggs_lbs_backward(int32_t N, int32_t J, int32_t K, const float* x, const fl
   {
     ProfScope ps(PROF_LBS_BWD, s);
     const int nblk = (J - 1 + LB_BONES - 1) / LB_BONES;
-    if (K > 0) hipLaunchKernelGGL(lbs_backward_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a);
+    if (J > MAX_J) {
+      if (K > 0) hipLaunchKernelGGL(lbs_backward_wide_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a);
+      else {
+        const int blocks = (N + LB_GPB - 1) / LB_GPB;
+        if (a.weight_mod) hipLaunchKernelGGL(lbs_backward_bonelane_wide_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(lbs_backward_bonelane_wide_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(lbs_backward_finish_kernel, dim3((J - 1) * 13 + 3), dim3(256), 0, s, a, blocks);
+      }
+    } else if (K > 0) hipLaunchKernelGGL(lbs_backward_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a);
     else switch (nblk) {
       case 1: launch_lbs_bwd_bonelane<1>(a, s); break;
       case 2: launch_lbs_bwd_bonelane<2>(a, s); break;

@@ -1,4 +1,4 @@
-// Forward kinematics over <= 64 joints on one wave64, device side: shared by the FK kernels (deform.hip), the skinning forward that runs the
+// Forward kinematics over <= 64 joints on one wave64 (<= 256 on one workgroup: fk_block_*), device side: shared by the FK kernels (deform.hip), the skinning forward that runs the
 // chain itself, and the PoseMLP backward that runs the reverse sweep in front of its own chain (pose_mlp.hip).
 //   quaternion_to_matrix      utils/time_utils.py:115-132
 //   chain_product_transform   skeleton_utils/skeleton_warp.py:242-273
@@ -229,6 +229,215 @@ __device__ __forceinline__ void fk_wave_backward(int J, const FkIn& in, const Fk
     dq[2] = s * gj - s2 * qj * dotA;
     dq[3] = s * gk - s2 * qk * dotA;
   }
+}
+
+// fk_load for joint j = the thread (fk_block_*)
+__device__ __forceinline__ void fk_load_joint(int j, int J, const float* __restrict__ local_rot, const float* __restrict__ joints,
+                                              const int32_t* __restrict__ parents, const float* __restrict__ dL_dG_in,
+                                              const float* __restrict__ dL_dnodes, FkIn& in, const float* __restrict__ transforms) {
+  in.par = 0;
+#pragma unroll
+  for (int e = 0; e < 4; e++) in.q[e] = (e == 0) ? 1.f : 0.f;
+#pragma unroll
+  for (int e = 0; e < 3; e++) { in.c[e] = 0.f; in.x[e] = 0.f; in.gn[e] = 0.f; }
+#pragma unroll
+  for (int e = 0; e < 12; e++) { in.dG[e] = 0.f; in.G[e] = 0.f; }
+  if (j < J) {
+    if (transforms) {
+#pragma unroll
+      for (int e = 0; e < 12; e++) in.G[e] = transforms[12 * j + e];
+    }
+    const int vp = (j == 0) ? 0 : parents[j];  // skeleton_warp.py:246-247
+    in.par = vp;
+#pragma unroll
+    for (int e = 0; e < 4; e++) in.q[e] = local_rot[4 * j + e];
+#pragma unroll
+    for (int e = 0; e < 3; e++) { in.x[e] = joints[3 * j + e]; in.c[e] = joints[3 * vp + e]; }
+    if (dL_dG_in) {
+#pragma unroll
+      for (int e = 0; e < 12; e++) in.dG[e] = dL_dG_in[12 * j + e];
+    }
+    if (dL_dnodes) {
+#pragma unroll
+      for (int e = 0; e < 3; e++) in.gn[e] = dL_dnodes[3 * j + e];
+    }
+  }
+}
+// T_j = [R | c - R c]: the joint's rotation about its PARENT joint (skeleton_warp.py:249-258)
+__device__ __forceinline__ void fk_local_T(const FkIn& in, float (&T)[12]) {
+  float q[4] = {in.q[0], in.q[1], in.q[2], in.q[3]};
+  float R[9];
+  quat_to_R_unnorm(q, R);
+  const float cx = in.c[0], cy = in.c[1], cz = in.c[2];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2];
+    const float c = (r == 0) ? cx : (r == 1 ? cy : cz);
+    T[4 * r + 3] = c - (R[3 * r] * cx + R[3 * r + 1] * cy + R[3 * r + 2] * cz);  // rotate about the PARENT joint
+  }
+}
+
+// dT_j (dL/d of the joint's local transform) -> dq = dL/dlocal_rot through t = c - R c and quaternion_to_matrix
+__device__ __forceinline__ void fk_dq_from_dT(bool on, const FkIn& in, const float (&dT)[12], float (&dq)[4]) {
+  dq[0] = 0.f; dq[1] = 0.f; dq[2] = 0.f; dq[3] = 0.f;
+  if (on) {
+    const float cc[3] = {in.c[0], in.c[1], in.c[2]};
+    float dR[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) dR[3 * a + b] = dT[4 * a + b] - dT[4 * a + 3] * cc[b];  // t = c - R c
+    const float qr = in.q[0], qi = in.q[1], qj = in.q[2], qk = in.q[3];
+    const float n = qr * qr + qi * qi + qj * qj + qk * qk;
+    const float s = 2.0f / n;
+    // A = (R - I)/s
+    const float A[9] = {-(qj * qj + qk * qk), qi * qj - qk * qr, qi * qk + qj * qr,
+                        qi * qj + qk * qr, -(qi * qi + qk * qk), qj * qk - qi * qr,
+                        qi * qk - qj * qr, qj * qk + qi * qr, -(qi * qi + qj * qj)};
+    float dotA = 0.f;
+#pragma unroll
+    for (int e = 0; e < 9; e++) dotA += dR[e] * A[e];
+    const float gr = -qk * dR[1] + qj * dR[2] + qk * dR[3] - qi * dR[5] - qj * dR[6] + qi * dR[7];
+    const float gi = qj * dR[1] + qk * dR[2] + qj * dR[3] - 2.f * qi * dR[4] - qr * dR[5] + qk * dR[6] + qr * dR[7] - 2.f * qi * dR[8];
+    const float gj = -2.f * qj * dR[0] + qi * dR[1] + qr * dR[2] + qi * dR[3] + qk * dR[5] - qr * dR[6] + qk * dR[7] - 2.f * qj * dR[8];
+    const float gk = -2.f * qk * dR[0] - qr * dR[1] + qi * dR[2] + qr * dR[3] - 2.f * qk * dR[4] + qj * dR[5] + qi * dR[6] + qj * dR[7];
+    const float s2 = s * s;
+    dq[0] = s * gr - s2 * qr * dotA;
+    dq[1] = s * gi - s2 * qi * dotA;
+    dq[2] = s * gj - s2 * qj * dotA;
+    dq[3] = s * gk - s2 * qk * dotA;
+  }
+}
+
+// ---- the chain over up to 256 joints on ONE workgroup of 256 threads (skeletons of 65..256 joints; <= 64 run the wave form
+// above).  Thread j owns joint j, and the LDS takes the place of the shuffles: depths by pointer doubling (8 steps), the
+// children as a 256-bit mask per parent, the forward sweep G_i = G_parent(i) T_i level by level with a barrier per level, and
+// the reverse sweep in which a parent adds its children's contributions in descending child index — the wave form's
+// arithmetic per joint and order per sum.  Lanes >= J carry harmless values; call with all 256 threads.
+#define MAX_J_WIDE 256
+#define FK_WIDE_WORDS (MAX_J_WIDE / 32)
+struct FkWideShared {
+  float G[MAX_J_WIDE][12];              // global transforms
+  float A[MAX_J_WIDE][12];              // (backward) what a joint hands its parent
+  int d[MAX_J_WIDE], anc[MAX_J_WIDE];   // pointer doubling
+  uint32_t kids[MAX_J_WIDE][FK_WIDE_WORDS];
+  int maxlev;
+};
+struct FkWide {
+  float T[12];  // local transform of the thread's joint
+  int par, lev, maxlev;
+};
+
+__device__ __forceinline__ void fk_block_forward(int J, const FkIn& in, FkWide& f, FkWideShared& sh, bool have_G = false) {
+  const int j = threadIdx.x;
+  const bool on = j < J;
+  f.par = 0;
+#pragma unroll
+  for (int e = 0; e < 12; e++) f.T[e] = 0.f;
+  if (on) {
+    f.par = in.par;
+    fk_local_T(in, f.T);
+  }
+#pragma unroll
+  for (int w = 0; w < FK_WIDE_WORDS; w++) sh.kids[j][w] = 0u;
+  if (j == 0) sh.maxlev = 0;
+  int d = (on && j >= 1) ? 1 : 0, anc = f.par;
+  sh.d[j] = d; sh.anc[j] = anc;
+  __syncthreads();
+  if (on && j >= 1) atomicOr(&sh.kids[f.par][j >> 5], 1u << (j & 31));
+  for (int s = 0; s < 8; s++) {
+    const int d2 = sh.d[anc], a2 = sh.anc[anc];
+    __syncthreads();
+    d += d2; anc = a2;
+    sh.d[j] = d; sh.anc[j] = anc;
+    __syncthreads();
+  }
+  f.lev = d;
+  if (d > 0) atomicMax(&sh.maxlev, d);
+#pragma unroll
+  for (int e = 0; e < 12; e++) sh.G[j][e] = have_G ? in.G[e] : f.T[e];
+  __syncthreads();
+  f.maxlev = sh.maxlev;
+  // G_i = G_parent(i) * T_i, level l reads level l - 1 (written before the last barrier)
+  for (int l = 1; !have_G && l <= f.maxlev; l++) {
+    if (on && f.lev == l) {
+      float Gp[12];
+#pragma unroll
+      for (int e = 0; e < 12; e++) Gp[e] = sh.G[f.par][e];
+      float G[12];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          float v = Gp[4 * r] * f.T[c] + Gp[4 * r + 1] * f.T[4 + c] + Gp[4 * r + 2] * f.T[8 + c];
+          if (c == 3) v += Gp[4 * r + 3];
+          G[4 * r + c] = v;
+        }
+#pragma unroll
+      for (int e = 0; e < 12; e++) sh.G[j][e] = G[e];
+    }
+    __syncthreads();
+  }
+}
+
+// The reverse sweep over the block (after fk_block_forward): -> dq = dL/dlocal_rot of the thread's joint.
+__device__ __forceinline__ void fk_block_backward(int J, const FkIn& in, const FkWide& f, FkWideShared& sh, float (&dq)[4]) {
+  const int j = threadIdx.x;
+  const bool on = j < J;
+  float dG[12];
+#pragma unroll
+  for (int e = 0; e < 12; e++) dG[e] = 0.f;
+  if (on) {
+    const float x = in.x[0], y = in.x[1], z = in.x[2];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const float e = in.gn[r];  // posed_j = G_j [joint_j; 1]
+      dG[4 * r] = in.dG[4 * r] + e * x;
+      dG[4 * r + 1] = in.dG[4 * r + 1] + e * y;
+      dG[4 * r + 2] = in.dG[4 * r + 2] + e * z;
+      dG[4 * r + 3] = in.dG[4 * r + 3] + e;
+    }
+  }
+  // deepest level first: the joints of level l + 1 (their dG is final) hand  [dR_G R_T^T + dt_G t_T^T | dt_G]  to their parents
+  for (int l = f.maxlev - 1; l >= 0; l--) {
+    if (on && f.lev == l + 1) {
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          float v;
+          if (c < 3) v = dG[4 * r] * f.T[4 * c] + dG[4 * r + 1] * f.T[4 * c + 1] + dG[4 * r + 2] * f.T[4 * c + 2] + dG[4 * r + 3] * f.T[4 * c + 3];
+          else v = dG[4 * r + 3];
+          sh.A[j][4 * r + c] = v;
+        }
+    }
+    __syncthreads();
+    if (on && f.lev == l) {
+      for (int w = FK_WIDE_WORDS - 1; w >= 0; w--) {
+        uint32_t km = sh.kids[j][w];
+        while (km != 0u) {
+          const int b = 31 - __builtin_clz(km);  // descending child index
+          const int i = 32 * w + b;
+#pragma unroll
+          for (int e = 0; e < 12; e++) dG[e] += sh.A[i][e];
+          km &= ~(1u << b);
+        }
+      }
+    }
+  }
+  // dT_j = Rp^T dG_j (both the rotation block and the translation column); the root's is its dG
+  float dT[12];
+  {
+    float Gp[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) Gp[e] = sh.G[f.par][e];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 4; c++)
+        dT[4 * r + c] = (j == 0) ? dG[4 * r + c] : Gp[r] * dG[c] + Gp[4 + r] * dG[4 + c] + Gp[8 + r] * dG[8 + c];
+  }
+  fk_dq_from_dT(on, in, dT, dq);
 }
 
 }  // namespace riggs

@@ -14,7 +14,7 @@ namespace riggs {
 
 #define PM_MAX_LAYERS 12
 #define PM_MAX_W 256
-#define PM_MAX_HEAD 320  // rows of the two heads together (4 J + 3): J <= 79 in the one-launch kernels
+#define PM_MAX_HEAD 320  // rows of the two heads together (4 J + 3) in the one-launch kernels; the layered ones take 4 * 256 + 3
 #define PM_MAX_IN 320
 #define PM_MAX_EMB 64
 #define PM_RPW 8       // rows per wave per pass (forward GEMV)
@@ -473,6 +473,27 @@ __global__ __launch_bounds__(256) void pm_fixed_add_kernel(int J, const float* _
   __syncthreads();
   if (t == 0 && loss_out) loss_out[0] = ((s_p[0] + s_p[1]) + (s_p[2] + s_p[3])) / (float)(4 * J);
 }
+// dst += src over n floats (the layered backward_fk: the heads' extra rotation gradient onto the chain's)
+__global__ __launch_bounds__(256) void pm_add_kernel(int n, const float* __restrict__ src, float* __restrict__ dst) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] += src[i];
+}
+
+// ... for more than 64 joints (4 J > 256 entries: a thread walks several)
+__global__ __launch_bounds__(256) void pm_fixed_add_wide_kernel(int J, const float* __restrict__ local_rot, const float* __restrict__ coef,
+                                                                float* __restrict__ dq, float* __restrict__ loss_out) {
+  __shared__ float s_p[4];
+  float ss = 0.f;
+  for (int t = threadIdx.x; t < 4 * J; t += 256) {
+    const float d = local_rot[t] - ((t & 3) == 0 ? 1.f : 0.f);
+    if (coef) dq[t] += coef[0] * d;
+    ss += d * d;
+  }
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss_out) loss_out[0] = ((s_p[0] + s_p[1]) + (s_p[2] + s_p[3])) / (float)(4 * J);
+}
 #undef PM_FAULT_BIT
 #define PM_FAULT_BIT 2u
 __global__ __launch_bounds__(PMF_WAVES * 64) void pm_backward_fused_kernel(PoseMlpDesc d, PoseMlpGradDesc g, PmFkArgs fk,
@@ -673,7 +694,7 @@ static int pm_fill(PoseMlpDesc& d, int32_t depth, int32_t width, int32_t multire
   RIGGS_REQUIRE(depth >= 1 && depth <= PM_MAX_LAYERS, "PoseMLP depth out of range");
   RIGGS_REQUIRE(width >= 1 && width <= PM_MAX_W, "PoseMLP width must be <= 256");
   RIGGS_REQUIRE(multires >= 0 && 1 + 2 * multires <= PM_MAX_EMB, "PoseMLP multires out of range");
-  RIGGS_REQUIRE(n_rot >= 1 && n_rot + 3 <= PM_MAX_HEAD, "PoseMLP rotation head too wide");
+  RIGGS_REQUIRE(n_rot >= 1 && n_rot <= 4 * MAX_J_WIDE, "PoseMLP rotation head too wide");
   d.depth = depth; d.width = width; d.multires = multires; d.skip = skip; d.n_rot = n_rot;
   for (int l = 0; l < depth; l++) { d.W[l] = weights[l]; d.b[l] = biases[l]; }
   d.W_rot = W_rot; d.b_rot = b_rot; d.W_tr = W_tr; d.b_tr = b_tr;
@@ -703,6 +724,7 @@ int riggs_pose_mlp_set_trace(void* dev_u64x128) { g_pm_trace = (unsigned long lo
 // test networks with wide heads and anything larger run one launch per layer.
 static bool pm_one_launch(int32_t width, int32_t n_rot) {
   if (option(OPT_POSE_MLP_LAYERED)) return false;  // (a host re-running a frame whose hand-off was lost)
+  if (n_rot > 4 * MAX_J) return false;  // (more than 64 joints: the one-launch backward runs the one-wave chain)
   return n_rot + 3 <= width || (width >= 128 && n_rot + 3 <= PM_MAX_HEAD);
 }
 // acts: activations, then (256-byte aligned) the state of the one-launch kernels:
@@ -824,9 +846,13 @@ static int pm_backward_impl(int32_t depth, int32_t width, int32_t multires, int3
     else RIGGS_HIP_CHECK(hipMemsetAsync(fk.dgt_out, 0, 12, s));
     int rc2 = riggs_fk_backward(fk.J, fk.local_rot, fk.joints, fk.parents, fk.dG, fk.g_nodes, fk.dq_out, fk.dgt_out, stream);
     if (rc2) return rc2;
-    RIGGS_REQUIRE(g_rotation == nullptr, "riggs_pose_mlp_backward_fk: an extra rotation gradient needs the one-launch kernels");
+    if (g_rotation) {  // the extra rotation gradient joins the chain's, in front of the template term (as in the one-launch kernel)
+      hipLaunchKernelGGL(pm_add_kernel, dim3((4 * fk.J + 255) / 256), dim3(256), 0, s, 4 * fk.J, g_rotation, fk.dq_out);
+      RIGGS_HIP_CHECK(hipGetLastError());
+    }
     if (fk.fixed_coef || fk.fixed_loss_out) {
-      hipLaunchKernelGGL(pm_fixed_add_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
+      if (fk.J <= MAX_J) hipLaunchKernelGGL(pm_fixed_add_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
+      else hipLaunchKernelGGL(pm_fixed_add_wide_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
       RIGGS_HIP_CHECK(hipGetLastError());
     }
     g_rotation = fk.dq_out; g_translation = fk.dgt_out;
@@ -863,7 +889,7 @@ int riggs_pose_mlp_backward_fk(int32_t depth, int32_t width, int32_t multires, i
                                const float* g_translation, float* dL_dlocal_rot, float* dL_dglobal_trans,
                                const float* template_fixed_coef, float* template_fixed_loss, float* workspace,
                                float* flat_grads, void* sync_state, riggs_stream stream) {
-  RIGGS_REQUIRE(num_joints >= 1 && num_joints <= MAX_J && 4 * num_joints == n_rot, "the rotation head must predict one quaternion per joint");
+  RIGGS_REQUIRE(num_joints >= 1 && num_joints <= MAX_J_WIDE && 4 * num_joints == n_rot, "the rotation head must predict one quaternion per joint");
   RIGGS_REQUIRE(local_rot && joints && parents && dL_dtransforms, "riggs_pose_mlp_backward_fk: missing chain input");
   PmFkArgs fk;
   fk.J = num_joints; fk.local_rot = local_rot; fk.joints = joints; fk.parents = parents; fk.dG = dL_dtransforms;

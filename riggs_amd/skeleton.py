@@ -514,8 +514,8 @@ class SkeletonWarp(nn.Module):
             raise ValueError("skinning=True leaves the reference's SkeletonWarp without _node_radius (utils/time_utils.py:809) "
                              "and its deform_by_pose fails on node_radius: not a configuration of this path")
         J = joints.shape[0]
-        if J > 64:
-            raise ValueError("at most 64 joints are supported by the LDS-staged kernels")
+        if J > 256:
+            raise ValueError("at most 256 joints are supported by the LDS-staged kernels")
         self.K = K
         self.name = "node"
         # attributes of the base class (utils/time_utils.py:773-819), kept because callers and checkpoints read them
