@@ -55,12 +55,29 @@ def test_deform_matches_reference_golden(path):
         wh = np.take_along_axis(out["nn_weight"].cpu().numpy(), np.argsort(idx, 1), 1)
         wr = np.take_along_axis(g["nn_weight"], np.argsort(g["nn_idx"], 1), 1)
         U.assert_close(wh[rows], wr[rows], "nn_weight")
+        loss = (out["d_xyz"] * T(g["g_xyz"])).sum() + (out["d_rotation"] * T(g["g_rot"])).sum() \
+            + (out["d_nodes"] * T(g["g_nodes"])).sum()
+        loss.backward()
         if rows.all():  # gradients are only comparable when every row made the same choice
-            loss = (out["d_xyz"] * T(g["g_xyz"])).sum() + (out["d_rotation"] * T(g["g_rot"])).sum() \
-                + (out["d_nodes"] * T(g["g_nodes"])).sum()
-            loss.backward()
             U.assert_close(q.grad.cpu().numpy(), g["grad_local_rot"], "dL/dlocal_rotation")
             U.assert_close(sw._node_radius.grad.cpu().numpy(), g["grad_node_radius"], "dL/d_node_radius")
+        # every row: the kernel's selection in the float64 (d2, bound) order, and the gradients against the float64 deformation
+        # over that selection
+        from tests import skin_ref as R
+        sel = idx - 1
+        assert R.selection_violations(g["x"], g["joints"], g["parents"], sel) == 0, "top-K selection out of (d2, bound) order"
+        qd = torch.from_numpy(g["local_rot"]).double().requires_grad_(True)
+        gtd = torch.from_numpy(g["global_trans"]).double().requires_grad_(True)
+        rhod = torch.from_numpy(g["node_radius_log"]).double().requires_grad_(True)
+        md = torch.from_numpy(g["motion_mask"]).double().requires_grad_(True)
+        o = R.deform64(torch.from_numpy(g["x"]), torch.from_numpy(g["joints"]), torch.from_numpy(g["parents"]), rhod, qd, gtd, md,
+                       torch.from_numpy(sel))
+        ((o["d_xyz"] * torch.from_numpy(g["g_xyz"]).double()).sum() + (o["d_rotation"] * torch.from_numpy(g["g_rot"]).double()).sum()
+         + (o["d_nodes"] * torch.from_numpy(g["g_nodes"]).double()).sum()).backward()
+        U.assert_close(q.grad.cpu().numpy(), qd.grad.numpy(), "dL/dlocal_rotation (selection-aware)")
+        U.assert_close(gt.grad.cpu().numpy(), gtd.grad.numpy(), "dL/dglobal_trans (selection-aware)")
+        U.assert_close(sw._node_radius.grad.cpu().numpy(), rhod.grad.numpy(), "dL/d_node_radius (selection-aware)")
+        U.assert_close(mask.grad.cpu().numpy(), md.grad.numpy(), "dL/dmotion_mask (selection-aware)")
         return
     U.assert_close(out["d_xyz"].detach().cpu().numpy(), g["d_xyz"], "d_xyz")
     U.assert_close(out["d_rotation"].detach().cpu().numpy(), g["d_rotation"], "d_rotation")
