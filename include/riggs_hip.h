@@ -604,6 +604,40 @@ int riggs_cnode_backward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t
                          float* workspace, riggs_stream stream);
 
 /* =====================================================================
+ * Stage-1 node regularisers (csrc/node_reg.hip): ControlNodeWarp.arap_loss / elastic_loss / acc_loss
+ * (utils/time_utils.py:1080-1120) over cal_connectivity_from_points / cal_arap_error (utils/deform_utils.py:51-103, 187-198).
+ * Neighbour lists are padded (M, K) int32 with -1 for dropped edges; nothing is compacted.  M <= 8192, T <= 16, K <= 15.
+ * Every backward is deterministic (no float atomics); losses are single device floats, upstream gradients device pointers.
+ *
+ * riggs_node_knn: for each of M points (D <= 16 coordinates, row stride `stride` floats) the Kq <= 16 smallest squared distances
+ * to all M points, ascending, ties to the lowest index; column 0 dropped when drop_first; with radius2 > 0, columns
+ * >= least_edge_num (after the drop) whose distance is not below radius2 become -1 / inf.  Columns beyond the point count are
+ * -1 / inf.  Writes nn_idx, nn_dist (M, Kq - drop_first).
+ * riggs_arap_*: seq (T, M, 3) node positions (t = 0 the source), nn_idx (M, K), rows (Ns) sample rows; forward writes the
+ * rotations rot (Ns, T, 9; t = 0 unused) and loss = sum_{s, t >= 1, n} |tgt - R src|^2 over kept edges; backward holds rot
+ * constant and writes g_seq (T, M, 3).  workspace: riggs_arap_workspace_floats floats.
+ * riggs_elastic_*: nodes_t (M, T, 3), nn_idx (M, K), weight (M, K): loss = mean_m sum_k w var_T|edge| / (var + 1e-5) (unbiased
+ * variance, the denominator held constant); backward writes g_nodes_t (M, T, 3) and g_weight (M, K).
+ * riggs_acc_*: nodes_t (M, 3, 3): loss = mean_m |n0 + n2 - 2 n1| / (that + 1e-5); backward writes g_nodes_t (M, 3, 3).
+ * ARAP / elastic: neighbour and sample-row indices outside [0, M) count as dropped edges (they are never dereferenced).
+ * ===================================================================== */
+int riggs_node_knn(int32_t M, int32_t D, int32_t stride, int32_t Kq, int32_t drop_first, int32_t least_edge_num, float radius2,
+                   const float* points, int32_t* nn_idx, float* nn_dist, riggs_stream stream);
+size_t riggs_arap_workspace_floats(int32_t M, int32_t T, int32_t K, int32_t Ns);
+int riggs_arap_forward(int32_t M, int32_t T, int32_t K, int32_t Ns, const float* seq, const int32_t* nn_idx, const int32_t* rows,
+                       float* rot, float* loss, float* workspace, riggs_stream stream);
+int riggs_arap_backward(int32_t M, int32_t T, int32_t K, int32_t Ns, const float* seq, const int32_t* nn_idx, const int32_t* rows,
+                        const float* rot, const float* g_loss, float* g_seq, float* workspace, riggs_stream stream);
+size_t riggs_elastic_workspace_floats(int32_t M, int32_t T, int32_t K);
+int riggs_elastic_forward(int32_t M, int32_t T, int32_t K, const float* nodes_t, const int32_t* nn_idx, const float* weight,
+                          float* loss, float* workspace, riggs_stream stream);
+int riggs_elastic_backward(int32_t M, int32_t T, int32_t K, const float* nodes_t, const int32_t* nn_idx, const float* weight,
+                           const float* g_loss, float* g_nodes_t, float* g_weight, float* workspace, riggs_stream stream);
+size_t riggs_acc_workspace_floats(int32_t M);
+int riggs_acc_forward(int32_t M, const float* nodes_t, float* loss, float* workspace, riggs_stream stream);
+int riggs_acc_backward(int32_t M, const float* nodes_t, const float* g_loss, float* g_nodes_t, riggs_stream stream);
+
+/* =====================================================================
  * simple_knn._C.distCUDA2 (scene/gaussian_model.py:20,170): mean squared distance to the 3
  * nearest neighbours.  points (P,3) -> out (P,).  workspace: riggs_knn_workspace_bytes(P).
  * ===================================================================== */

@@ -232,6 +232,16 @@ _SIGS = {
     "riggs_knn_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "riggs_dist2_knn3": (C.c_int, [C.c_int32, _P, _P, _P, _P]),
     "riggs_dist2_knn3_bruteforce": (C.c_int, [C.c_int32, _P, _P, _P]),
+    "riggs_node_knn": (C.c_int, [C.c_int32] * 6 + [C.c_float] + [_P] * 4),
+    "riggs_arap_workspace_floats": (C.c_size_t, [C.c_int32] * 4),
+    "riggs_arap_forward": (C.c_int, [C.c_int32] * 4 + [_P] * 7),
+    "riggs_arap_backward": (C.c_int, [C.c_int32] * 4 + [_P] * 8),
+    "riggs_elastic_workspace_floats": (C.c_size_t, [C.c_int32] * 3),
+    "riggs_elastic_forward": (C.c_int, [C.c_int32] * 3 + [_P] * 6),
+    "riggs_elastic_backward": (C.c_int, [C.c_int32] * 3 + [_P] * 8),
+    "riggs_acc_workspace_floats": (C.c_size_t, [C.c_int32]),
+    "riggs_acc_forward": (C.c_int, [C.c_int32] + [_P] * 4),
+    "riggs_acc_backward": (C.c_int, [C.c_int32] + [_P] * 4),
 }
 
 

@@ -18,6 +18,8 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import node_reg as NR
+from .node_gaussians import NodeGaussians
 
 LOCAL_FRAME, ROT_AS_RES = 1, 2
 
@@ -201,27 +203,262 @@ class StaticNodeNetwork(nn.Module):
                 "d_opacity": None, "d_color": None}
 
 
-class ControlNodeWarp(nn.Module):
+class ControlNodeWarp(NodeGaussians, nn.Module):
     """``ControlNodeWarp`` (time_utils.py:770-1236) for the shipped configuration: parameters ``nodes`` (M, 3 + hyper_dim),
     ``_node_radius`` (M), ``_node_weight`` (M, 1) with the reference's names and activations; ``network`` is the node network
-    (a torch module ``(nodes_xyz, t) -> dict``; default: the static one)."""
+    (a torch module ``(nodes_xyz, t) -> dict``; default: the static one).  The stage-1 trainer's lifecycle (``init``,
+    ``densify``, the node Gaussians, ``state_dict``) and node regularisers (``arap_loss`` / ``elastic_loss`` / ``acc_loss`` over
+    csrc/node_reg.hip, no host synchronisation) have the reference's names and signatures."""
 
     def __init__(self, node_num=512, K=3, with_node_weight=True, local_frame=False, d_rot_as_res=True, hyper_dim=2, network=None,
-                 pred_opacity=False, pred_color=False, skinning=False, **kwargs):
+                 pred_opacity=False, pred_color=False, skinning=False, is_blender=False, init_pcl=None, use_hash=False,
+                 hash_time=False, enable_densify_prune=False, with_arap_loss=False, is_scene_static=False, **kwargs):
         super().__init__()
+        if use_hash:
+            raise NotImplementedError("use_hash: the hash-grid node network needs tinycudann, which is not part of this library")
         if skinning and local_frame:
             raise NotImplementedError("skinning with local_frame: the reference's own forward fails there (its einsum expects per-"
                                       "Gaussian neighbour lists, time_utils.py:1152)")
+        self.name = "node"
+        self.is_blender, self.use_hash, self.hash_time = is_blender, use_hash, hash_time
+        self.enable_dp, self.is_scene_static = enable_densify_prune, is_scene_static
         self.skinning, self.pred_opacity, self.pred_color = bool(skinning), bool(pred_opacity), bool(pred_color)
         hyper_dim = 0 if skinning else hyper_dim  # "skinning should not be with hyper" (time_utils.py:782)
         self.K, self.with_node_weight, self.local_frame, self.d_rot_as_res, self.hyper_dim = K, with_node_weight, local_frame, d_rot_as_res, hyper_dim
-        self.network = network if network is not None else StaticNodeNetwork()
+        if with_arap_loss and not is_scene_static:  # (time_utils.py:790-795)
+            self.lambda_arap_landmarks = [1e-4, 1e-4, 1e-5, 1e-5, 0]
+            self.lambda_arap_steps = [0, 5000, 10000, 20000, 20001]
+        else:
+            self.lambda_arap_landmarks, self.lambda_arap_steps = [0], [0]
+        self.network = network if (network is not None and not is_scene_static) else StaticNodeNetwork()
+        self.register_buffer("inited", torch.tensor(False))
         self.nodes = nn.Parameter(torch.randn(node_num, 3 + hyper_dim))
         if not skinning:  # (time_utils.py:807-810)
             self._node_radius = nn.Parameter(torch.randn(node_num))
             if with_node_weight:
                 self._node_weight = nn.Parameter(torch.zeros(node_num, 1))
         self.reg_loss = 0.
+        if init_pcl is not None:
+            self.init(None, init_pcl)
+        self.nodes_color_visualization = torch.ones_like(self.nodes)
+        self.cached_nn_weight = False
+        self.nn_weight, self.nn_dist, self.nn_idxs = None, None, None
+
+    def update(self, iteration):
+        if hasattr(self.network, "update"):
+            self.network.update(iteration)
+
+    @property
+    def param_names(self):
+        if self.skinning:
+            return ["nodes", "deform"]
+        return ["nodes", "_node_radius", "_node_weight"] if self.with_node_weight else ["nodes", "_node_radius"]
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Node parameters are assigned (re-created when the node count differs), ``gs_*`` entries go to the node Gaussians, the
+        rest is loaded non-strictly (time_utils.py:844-865)."""
+        state_dict = dict(state_dict)
+        names = self.param_names
+        for key in list(state_dict):
+            if key in names:
+                v = state_dict[key]
+                if getattr(self, key).shape != v.shape:
+                    print(f"Loading nodes mismatching the original setting: {getattr(self, key).shape} and {v.shape}")
+                    setattr(self, key, nn.Parameter(v))
+                else:
+                    getattr(self, key).data = v
+            elif key.startswith("gs_"):
+                try:
+                    getattr(self.as_gaussians, key[3:]).data = state_dict[key]
+                except Exception:
+                    print(f"Directly set as values for {key} when loading deform gaussians")
+                    setattr(self.as_gaussians, key[3:], state_dict[key])
+        for key in names:
+            state_dict.pop(key, None)
+        return super().load_state_dict(state_dict, strict=False)
+
+    def init(self, opt, init_pcl, hyper_pcl=None, keep_all=False, force_init=False, as_gs_force_with_motion_mask=False,
+             force_gs_keep_all=False, reset_bbox=True, **kwargs):
+        """Nodes from the initial point cloud (time_utils.py:874-922): all of it (``keep_all``, or fewer points than nodes:
+        new parameters, the optimizer must be set up again) or a farthest-point sample (random start) of it or of
+        ``hyper_pcl``; radius log(0.1 scene range), weights 0; then the node Gaussians, set up for training with ``opt``."""
+        from .gaussian_model import farthest_point_sample
+        if bool(self.inited) and not force_init:
+            return
+        self.inited.data = torch.ones_like(self.inited)
+        dev = init_pcl.device
+        if keep_all or self.node_num > init_pcl.shape[0]:
+            self.nodes = nn.Parameter(torch.cat([init_pcl.float(), 1e-2 * torch.ones(init_pcl.shape[0], self.hyper_dim, device=dev)], -1))
+            init_nodes_idx = None
+            print("Initialization with all pcl. Need to reset the optimizer.")
+        else:
+            pcl_to_samp = init_pcl if hyper_pcl is None else hyper_pcl
+            init_nodes_idx = farthest_point_sample(pcl_to_samp.detach()[None], self.node_num)[0]
+            self.nodes.data = torch.cat([init_pcl[init_nodes_idx].float(), 1e-2 * torch.ones(self.node_num, self.hyper_dim, device=dev)], -1)
+        scene_range = init_pcl.max() - init_pcl.min()
+        if self.skinning:
+            if "feature" in kwargs:
+                radius = .1 * scene_range + 1e-7
+                kwargs["feature"].data = -torch.log((init_pcl[:, None] - self.nodes[None, ..., :3]).square().sum(-1) / radius ** 2)
+        else:
+            radius = torch.log(.1 * scene_range + 1e-7) * torch.ones(self.node_num, device=dev)
+            if keep_all or self.node_num > init_pcl.shape[0]:
+                self._node_radius = nn.Parameter(radius)
+                self._node_weight = nn.Parameter(torch.zeros_like(self.nodes[:, :1]))
+            else:
+                self._node_radius.data = radius
+                self._node_weight.data = torch.zeros_like(self.nodes[:, :1])
+        self.gs = None
+        if force_gs_keep_all:
+            self.init_gaussians(init_pcl=init_pcl, with_motion_mask=as_gs_force_with_motion_mask)
+        else:
+            self.init_gaussians(init_pcl=self.nodes[..., :3], with_motion_mask=as_gs_force_with_motion_mask)
+        if opt is not None:
+            self.as_gaussians.training_setup(opt)
+        print(f"Control node initialized with {self.nodes.shape[0]} from {init_pcl.shape[0]} points.")
+        return init_nodes_idx
+
+    def cal_nn_weight(self, x, K=None, feature=None, nodes=None, gs_kernel=True, temperature=1.):
+        """(time_utils.py:934-964) the K nearest nodes of every row of ``x`` in (xyz, hyper) space and their weights.  Used by
+        ``cal_node_importance`` (once per densification); the per-step paths use the HIP kernels."""
+        if self.skinning:
+            return torch.softmax(feature, dim=-1), None, torch.arange(self.node_num, device=feature.device)
+        if self.cached_nn_weight and self.nn_weight is not None:
+            return self.nn_weight, self.nn_dist, self.nn_idxs
+        if self.hyper_dim > 0 and feature is not None:
+            x = torch.cat([x.detach(), feature[..., :self.hyper_dim]], dim=-1)
+        K = self.K if K is None else K
+        nodes = self.nodes[..., :3].detach() if nodes is None else nodes[..., :3]
+        if feature is not None:
+            nodes = torch.cat([nodes[..., :3].detach(), self.nodes[..., 3:]], dim=-1)
+        nn_dist, nn_idxs = _knn_sq(x, nodes, K)
+        if not gs_kernel:
+            return torch.softmax(-nn_dist / temperature, dim=-1), nn_dist, nn_idxs
+        nn_weight = torch.exp(-nn_dist / (2 * self.node_radius[nn_idxs] ** 2))
+        if self.with_node_weight:
+            nn_weight = nn_weight * self.node_weight[nn_idxs][..., 0]
+        nn_weight = nn_weight + 1e-7
+        nn_weight = nn_weight / nn_weight.sum(dim=-1, keepdim=True)
+        if self.cached_nn_weight:
+            self.nn_weight, self.nn_dist, self.nn_idxs = nn_weight, nn_dist, nn_idxs
+        return nn_weight, nn_dist, nn_idxs
+
+    @torch.no_grad()
+    def cal_node_importance(self, x, K=None, weights=None, feature=None):
+        """(time_utils.py:1270-1288) per node the weighted mean of its Gaussians' weights, their weighted mean position and the
+        sum of weights."""
+        if self.hyper_dim > 0:
+            x = torch.cat([x, feature[..., :self.hyper_dim]], dim=-1)
+        K = self.K if K is None else K
+        nn_weight, _, nn_idxs = self.cal_nn_weight(x=x[..., :3], K=K, feature=feature)
+        flat = nn_idxs.reshape(-1)
+        weights = torch.ones_like(x[:, 0]) if weights is None else weights
+        ww = nn_weight * weights[:, None]
+        node_importance = torch.zeros_like(self.nodes[:, 0]).index_add_(0, flat, ww.reshape(-1))
+        node_edge_count = torch.zeros_like(self.nodes[:, 0]).index_add_(0, flat, nn_weight.reshape(-1))
+        xs = x[:, None].expand(*nn_weight.shape, x.shape[-1]).reshape(-1, x.shape[-1])
+        avg_affected_x = torch.zeros_like(self.nodes).index_add_(0, flat, ww.reshape(-1, 1) * xs)
+        avg_affected_x = avg_affected_x / node_importance[:, None]
+        node_importance = node_importance / (node_edge_count + 1e-7)
+        return node_importance, avg_affected_x, node_edge_count
+
+    @torch.no_grad()
+    def densify(self, max_grad, optimizer, x, x_grad, feature=None, K=None, use_gaussians_grad=False, force_dp=False):
+        """(time_utils.py:1290-1383) add a node at the weighted mean position of the Gaussians of every node whose mean
+        gradient norm exceeds ``max_grad``, drop nodes no Gaussian uses; the optimizer's 'nodes' group (``param_names`` order)
+        and the node Gaussians follow."""
+        if not self.enable_dp and not force_dp:
+            return
+        if not bool(self.inited):
+            print("No need to densify nodes before initialization.")
+            return
+        if self.skinning:
+            print("No need to densify for skinning type")
+            return
+        x_grad[x_grad.isnan()] = 0.
+        K = self.K if K is None else K
+        weights = x_grad.norm(dim=-1)
+        node_avg_xgradnorm, node_avg_x, node_edge_count = self.cal_node_importance(x=x, K=K, weights=weights, feature=feature)
+        if use_gaussians_grad or not hasattr(self, "nodes_accumulated_grad"):
+            selected = torch.logical_and(node_avg_xgradnorm > max_grad, node_avg_x.isnan().logical_not().all(dim=-1))
+        else:
+            selected = self.nodes_accumulated_grad / self.denom > max_grad
+            self.nodes_accumulated_grad.data = 0
+            self.denom = 0
+        self.nodes_color_visualization = torch.ones_like(self.nodes[..., :3])
+        pruned = node_edge_count == 0
+        if selected.sum() > 0 or pruned.sum() > 0:
+            print(f"Add {selected.sum()} nodes and prune {pruned.sum()} nodes. ", end="")
+        else:
+            return
+        names = self.param_names
+
+        def surgery(make):
+            for group in optimizer.param_groups:
+                if group["name"] != "nodes":
+                    continue
+                for i, name in enumerate(names):
+                    old = group["params"][i]
+                    state = optimizer.state.get(old, None)
+                    new = nn.Parameter(make(i, old.detach()).requires_grad_(True))
+                    if state is not None:
+                        state["exp_avg"] = make(i, state["exp_avg"], zeros=True)
+                        state["exp_avg_sq"] = make(i, state["exp_avg_sq"], zeros=True)
+                        del optimizer.state[old]
+                        optimizer.state[new] = state
+                    group["params"][i] = new
+                    setattr(self, name, new)
+
+        if selected.sum() > 0:
+            new_nodes = node_avg_x[selected]
+            ext = [new_nodes, self._node_radius[selected]] + ([self._node_weight[selected]] if self.with_node_weight else [])
+            surgery(lambda i, t, zeros=False: torch.cat([t, torch.zeros_like(ext[i]) if zeros else ext[i]], 0))
+            self.nodes_color_visualization = torch.cat([self.nodes_color_visualization, torch.ones_like(new_nodes[..., :3])], 0)
+            self.nodes_color_visualization[-new_nodes.shape[0]:, 1:] = 0  # new nodes in red
+        if pruned.shape[0] < self.nodes.shape[0]:
+            pruned = torch.cat([pruned, torch.zeros(self.nodes.shape[0] - pruned.shape[0], dtype=pruned.dtype, device=pruned.device)])
+        keep = ~pruned
+        if pruned.sum() > 0:
+            self.nodes_color_visualization = self.nodes_color_visualization[keep]
+            surgery(lambda i, t, zeros=False: t[keep])
+        if not self.with_node_weight:
+            self._node_weight = torch.zeros_like(self.nodes[..., :1])
+        # (_xyz aliases the old nodes[..., :3], a strided view; the row gathers want dense rows — it is re-aliased below)
+        self.gs._xyz.data = self.gs._xyz.data.contiguous()
+        self.gs.densify_and_split(selected_pts_mask=selected, N=1, without_prune=True)
+        self.gs.prune_points(pruned)
+        self.gs._xyz.data = self.nodes[..., :3]
+        print(f"With {self.nodes.shape[0]} nodes left.")
+
+    # ---- node regularisers (time_utils.py:1080-1120) over csrc/node_reg.hip: device random numbers, no host sync -----------
+    def _t_center(self, t, delta_t):
+        dev = self.nodes.device
+        if t is None:
+            return torch.rand((), device=dev)
+        return t.squeeze() + delta_t * (torch.rand((), device=dev) - .5)
+
+    def _nodes_at(self, t_samp):
+        T = t_samp.shape[0]
+        node_trans = self.node_deform(t=t_samp[None, :, None].expand(self.node_num, T, 1))["d_xyz"]
+        return self.nodes[:, None, :3].detach() + node_trans  # M, T, 3
+
+    def arap_loss(self, t=None, delta_t=0.05, t_samp_num=2):
+        t = self._t_center(t, delta_t)
+        nodes_t = self._nodes_at(torch.rand(t_samp_num, device=self.nodes.device) * delta_t + t - .5 * delta_t)
+        nn_idx, _ = NR.connectivity_padded(nodes_t[:, 0].detach(), K=10)
+        return NR.arap_error_padded(nodes_t.permute(1, 0, 2), nn_idx)
+
+    def elastic_loss(self, t=None, delta_t=0.005, K=2, t_samp_num=8):
+        t = self._t_center(t, delta_t)
+        nodes_t = self._nodes_at(torch.rand(t_samp_num, device=self.nodes.device) * delta_t + t - .5 * delta_t)
+        nn_idx, _ = NR.node_knn(self.nodes[:, :3 + self.hyper_dim].detach(), K + 1)
+        w = NR.node_graph_weight(self.nodes, self._node_radius, self._node_weight if self.with_node_weight else None,
+                                 self.hyper_dim, nn_idx)
+        return NR.elastic_energy(nodes_t, nn_idx[:, 1:].contiguous(), w[:, 1:])
+
+    def acc_loss(self, t=None, delta_t=.005):
+        t = self._t_center(t, delta_t)
+        return NR.acc_energy(self._nodes_at(torch.stack([t - delta_t, t, t + delta_t])))
 
     @property
     def node_radius(self):
@@ -243,6 +480,9 @@ class ControlNodeWarp(nn.Module):
 
     def expand_time(self, t):
         return t.unsqueeze(0).expand(self.nodes.shape[0], -1)
+
+    def query_network(self, x, t, **kwargs):
+        return self.network(x=x, t=t, **kwargs)
 
     def node_deform(self, t, **kwargs):
         if t.dim() == 3:  # (M, T, 1): the nodes at T times each (time_utils.py:990-1002)
@@ -347,7 +587,8 @@ class ControlNodeWarp(nn.Module):
         out["d_rotation_bias"] = ((q_bias[idx] * w[..., None]).sum(dim=1) - rot_bias) * motion_mask + rot_bias
         return out
 
-    def forward(self, x, t, feature, motion_mask, animation_d_values=None, node_trans_bias=None, **kwargs):
+    def forward(self, x, t, feature, motion_mask, animation_d_values=None, node_trans_bias=None, iteration=0, is_training=True,
+                **kwargs):
         if t.dim() == 0:
             t = self.expand_time(t)
         node_attrs = dict(self.node_deform(t=t))
@@ -379,4 +620,8 @@ class ControlNodeWarp(nn.Module):
         out["d_nodes"] = self.nodes[..., :3] + node_attrs["d_xyz"]
         if node_trans_bias is not None:
             out = self._edit(x.detach(), t, out, node_attrs, node_trans_bias, motion_mask)
+        self.reg_loss = 0.
+        lambda_arap = NR.landmark_interpolate(self.lambda_arap_landmarks, self.lambda_arap_steps, iteration)
+        if self.training and lambda_arap > 0 and is_training:  # (time_utils.py:1229-1233)
+            self.reg_loss = self.reg_loss + self.arap_loss() * lambda_arap
         return out

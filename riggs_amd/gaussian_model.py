@@ -69,14 +69,14 @@ def strip_symmetric(m):  # upper triangle xx xy xz yy yz zz: utils/general_utils
     return torch.stack((m[:, 0, 0], m[:, 0, 1], m[:, 0, 2], m[:, 1, 1], m[:, 1, 2], m[:, 2, 2]), -1)
 
 
-def farthest_point_sample(xyz, npoint):
+def farthest_point_sample(xyz, npoint, start=None):
     """(B, N, C) -> (B, npoint) indices of an iterative farthest-point sweep from a random start
-    (utils/time_utils.py:461-482)."""
+    (utils/time_utils.py:461-482); ``start`` (B,) fixes the first index."""
     B, N, _ = xyz.shape
     dev = xyz.device
     picked = torch.zeros(B, npoint, dtype=torch.long, device=dev)
     nearest = torch.full((B, N), 1e10, device=dev)
-    cur = torch.randint(0, N, (B,), dtype=torch.long, device=dev)
+    cur = torch.randint(0, N, (B,), dtype=torch.long, device=dev) if start is None else torch.as_tensor(start, dtype=torch.long).to(dev)
     rows = torch.arange(B, device=dev)
     for i in range(npoint):
         picked[:, i] = cur
@@ -368,6 +368,10 @@ class GaussianModel:
             p = g["params"][0]
             st = self.optimizer.state.get(p, None)
             new_p = torch.empty((n_out,) + tuple(p.shape[1:]), dtype=torch.float32, device=dev)
+            if math.prod(p.shape[1:]) == 0:  # zero-width rows (f_rest at sh_degree 0): nothing to gather
+                st_m = (torch.empty_like(new_p), torch.empty_like(new_p)) if (st is not None and "exp_avg" in st) else None
+                owners.append((g, p, st, new_p, st_m))
+                continue
             src.append(p.detach().contiguous()); dst.append(new_p); width.append(max(1, p.numel() // max(1, p.shape[0])) if p.shape[0] else int(math.prod(p.shape[1:]))); zero_new.append(0)
             moments = None
             if st is not None and "exp_avg" in st:
@@ -520,3 +524,16 @@ class StandardGaussianModel(GaussianModel):
         s = self._scaling[..., :1].repeat(1, 3) if self.use_isotropic_gs else self._scaling
         mean = s.mean()[None, None] if self.all_the_same else s.mean(dim=1, keepdim=True)
         return self.scaling_activation(mean.expand_as(s))
+
+    def densify_and_split(self, grads=None, grad_threshold=None, scene_extent=None, N=2, selected_pts_mask=None, without_prune=False,
+                          unit_normals=None):
+        """The children's log-scales come from the shared (mean) scale, as the reference's get_scaling gives them (:461); the
+        base class's row kernel copies each parent's own row."""
+        if selected_pts_mask is None:
+            return super().densify_and_split(grads, grad_threshold, scene_extent, N, None, without_prune, unit_normals)
+        sel = selected_pts_mask.reshape(-1).bool()
+        shared = self.get_scaling.detach()[sel].repeat(N, 1) / (0.8 * N)
+        super().densify_and_split(grads, grad_threshold, scene_extent, N, selected_pts_mask, without_prune, unit_normals)
+        if shared.shape[0]:
+            new = self.scaling_inverse_activation(shared)
+            self._scaling.data[-shared.shape[0]:] = new[..., :self._scaling.shape[1]]

@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
+from .node_gaussians import NodeGaussians
 
 
 # --------------------------------------------------------------------------- PoseMLP (A1)
@@ -497,7 +498,7 @@ class _BaseNetworkPlaceholder(nn.Module):
         return
 
 
-class SkeletonWarp(nn.Module):
+class SkeletonWarp(NodeGaussians, nn.Module):
     """HIP-backed mirror of skeleton_utils/skeleton_warp.py:SkeletonWarp (:10-300) and of what it inherits from
     ``ControlNodeWarp`` (utils/time_utils.py:770-932, :1238-1260): constructor signature, attributes, state-dict keys,
     ``as_gaussians`` / ``init_gaussians`` / ``update`` — the surface ``scene/skeleton_model.py``, ``train_rig.py``,
@@ -596,45 +597,8 @@ class SkeletonWarp(nn.Module):
         return ["nodes", "_node_radius", "_node_weight"] if self.with_node_weight else ["nodes", "_node_radius"]
 
     # ---- the joints as a small Gaussian model (utils/time_utils.py:1238-1260): what SkeletonModel.train_setting sets an
-    # optimizer up for (scene/skeleton_model.py:38-39) and the GUI's skeleton-only view renders (interactive_GUI.py:265,391)
-    @staticmethod
-    def _gaussian_classes():
-        try:  # the trainer's own classes when this module runs inside a RigGS checkout
-            from scene.gaussian_model import BasicPointCloud, StandardGaussianModel
-        except Exception:
-            from .gaussian_model import BasicPointCloud, StandardGaussianModel
-        return BasicPointCloud, StandardGaussianModel
-
-    @property
-    def as_gaussians(self):
-        if getattr(self, "gs", None) is None:
-            print("Building Learnable Gaussians for Nodes!")
-            BasicPointCloud, StandardGaussianModel = self._gaussian_classes()
-            joints = self.nodes[..., :3].detach()
-            pcd = BasicPointCloud(points=joints, colors=torch.zeros_like(joints), normals=joints)
-            self.gs = StandardGaussianModel(sh_degree=0, all_the_same=True, with_motion_mask=False)
-            self.gs.create_from_pcd(pcd=pcd, spatial_lr_scale=0.0, print_info=False)  # distCUDA2 on J points
-            self.gs._scaling.data = torch.log(1e-2 * torch.ones_like(self.gs._scaling))
-            self.gs._xyz.data = self.nodes[..., :3]
-        return self.gs
-
-    def init_gaussians(self, init_pcl, with_motion_mask):
-        if getattr(self, "gs", None) is None:
-            print("Initialize Learnable Gaussians for Nodes with Point Clouds!")
-            BasicPointCloud, StandardGaussianModel = self._gaussian_classes()
-            pcd = BasicPointCloud(points=init_pcl.detach(), colors=torch.zeros_like(init_pcl), normals=torch.zeros_like(init_pcl))
-            self.gs = StandardGaussianModel(sh_degree=0, all_the_same=True, with_motion_mask=with_motion_mask)
-            self.gs.create_from_pcd(pcd=pcd, spatial_lr_scale=0.0, print_info=False)
-        return self.gs
-
-    def state_dict(self, *args, **kwargs):
-        """The module's entries plus, once the joint Gaussians exist, theirs as ``gs_<name>`` (utils/time_utils.py:867-872)."""
-        sd = super().state_dict(*args, **kwargs)
-        if getattr(self, "gs", None) is not None:
-            prefix = kwargs.get("prefix", args[1] if len(args) > 1 else "")
-            for name in self.gs.param_names():
-                sd[prefix + "gs_" + name] = getattr(self.gs, name)
-        return sd
+    # optimizer up for (scene/skeleton_model.py:38-39) and the GUI's skeleton-only view renders (interactive_GUI.py:265,391);
+    # as_gaussians / init_gaussians / state_dict come from NodeGaussians
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         """Accepts the reference's ``skeleton.pth`` (utils/time_utils.py:844-865): node parameters are assigned (re-created
