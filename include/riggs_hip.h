@@ -638,6 +638,51 @@ int riggs_acc_forward(int32_t M, const float* nodes_t, float* loss, float* works
 int riggs_acc_backward(int32_t M, const float* nodes_t, const float* g_loss, float* g_nodes_t, riggs_stream stream);
 
 /* =====================================================================
+ * Stage-1 node network (csrc/node_mlp.hip): DeformNetwork (utils/time_utils.py:310-458) in fp32 on the matrix pipe.
+ *   x_emb = PE_10(x) (63 columns); is_blender: t_emb = timenet(PE_6(t)) (13 -> 256 -> ReLU -> 30), else PE_10(t) (21);
+ *   trunk: 8 Linear + ReLU of `width`, the embedded input concatenated in front of the output of layer 4;
+ *   heads on the last activation: warp (3), scaling (3; max_d_scale > 0: tanh(.) * log(max_d_scale)), rotation (4),
+ *   local_rotation (4, optional), opacity (1, optional): head_w / head_b in that order, NULL for an absent head.
+ * Every weight is the fp32 master, row-major (out, in) as nn.Linear keeps it, and is read in place by every call: no copy is
+ * kept, so nothing can go stale when an optimizer writes the masters between two calls.
+ * width in {64, 128, 256}, depth 8, 1 <= R <= 65536 rows per call; anything else is rejected.  x (R, 3); t: R floats
+ * (t_stride 1) or one float shared by every row (t_stride 0).  The inputs are not differentiated.
+ * forward (one launch) writes the head outputs (contiguous (R, 3 / 3 / 4 / 4 / 1); a pointer per head present, NULL otherwise)
+ * and `acts` (riggs_node_mlp_acts_floats floats: the embedded input, the time net's hidden row, the eight post-ReLU
+ * activations; the last of them, the reference's `hidden` (R, width), starts at float riggs_node_mlp_hidden_offset).
+ * backward (two launches) takes one cotangent per head (NULL: zero) and writes EVERY parameter gradient (overwriting) through
+ * `grads`, shaped like the parameters; `workspace`: riggs_node_mlp_backward_workspace_floats floats.  Deterministic: each
+ * (layer, 32 x 32 tile) of a weight gradient is one workgroup whose four waves walk the four quarters of the rows in ascending
+ * order, added in wave order; no float atomics.
+ * No host synchronisation, no allocation: capturable into a hipGraph.
+ * ===================================================================== */
+typedef struct riggs_node_mlp {
+  int32_t width, depth, is_blender;
+  float max_d_scale;                       /* <= 0: the scaling head is returned as it is */
+  const float *tn_w0, *tn_b0, *tn_w1, *tn_b1; /* timenet.0 (256, 13), timenet.2 (30, 256); is_blender only */
+  const float* w[8];                       /* linear.0 .. linear.7 */
+  const float* b[8];
+  const float* head_w[5];                  /* gaussian_warp, gaussian_scaling, gaussian_rotation, local_rotation, gaussian_opacity */
+  const float* head_b[5];
+} riggs_node_mlp;
+typedef struct riggs_node_mlp_grads {
+  float *tn_w0, *tn_b0, *tn_w1, *tn_b1;
+  float* w[8];
+  float* b[8];
+  float* head_w[5];
+  float* head_b[5];
+} riggs_node_mlp_grads;
+size_t riggs_node_mlp_acts_floats(int32_t R, int32_t width, int32_t depth);
+size_t riggs_node_mlp_hidden_offset(int32_t R, int32_t width, int32_t depth);
+size_t riggs_node_mlp_backward_workspace_floats(int32_t R, int32_t width, int32_t depth);
+int riggs_node_mlp_forward(const riggs_node_mlp* net, int32_t R, const float* x, const float* t, int32_t t_stride, float* acts,
+                           float* d_xyz, float* d_scaling, float* d_rotation, float* local_rotation, float* d_opacity,
+                           riggs_stream stream);
+int riggs_node_mlp_backward(const riggs_node_mlp* net, int32_t R, const float* acts, const float* g_xyz, const float* g_scaling,
+                            const float* g_rotation, const float* g_local_rotation, const float* g_opacity, float* workspace,
+                            const riggs_node_mlp_grads* grads, riggs_stream stream);
+
+/* =====================================================================
  * simple_knn._C.distCUDA2 (scene/gaussian_model.py:20,170): mean squared distance to the 3
  * nearest neighbours.  points (P,3) -> out (P,).  workspace: riggs_knn_workspace_bytes(P).
  * ===================================================================== */

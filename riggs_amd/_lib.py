@@ -135,6 +135,21 @@ class FrameGate:
 _lib = None
 
 _P = C.c_void_p
+
+
+class NodeMlp(C.Structure):
+    """riggs_node_mlp (include/riggs_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("depth", C.c_int32), ("is_blender", C.c_int32), ("max_d_scale", C.c_float),
+                ("tn_w0", _P), ("tn_b0", _P), ("tn_w1", _P), ("tn_b1", _P),
+                ("w", _P * 8), ("b", _P * 8), ("head_w", _P * 5), ("head_b", _P * 5)]
+
+
+class NodeMlpGrads(C.Structure):
+    """riggs_node_mlp_grads (include/riggs_hip.h)."""
+    _fields_ = [("tn_w0", _P), ("tn_b0", _P), ("tn_w1", _P), ("tn_b1", _P),
+                ("w", _P * 8), ("b", _P * 8), ("head_w", _P * 5), ("head_b", _P * 5)]
+
+
 _SIGS = {
     "riggs_version": (C.c_int, []),
     "riggs_last_error": (C.c_char_p, []),
@@ -242,6 +257,11 @@ _SIGS = {
     "riggs_acc_workspace_floats": (C.c_size_t, [C.c_int32]),
     "riggs_acc_forward": (C.c_int, [C.c_int32] + [_P] * 4),
     "riggs_acc_backward": (C.c_int, [C.c_int32] + [_P] * 4),
+    "riggs_node_mlp_acts_floats": (C.c_size_t, [C.c_int32] * 3),
+    "riggs_node_mlp_hidden_offset": (C.c_size_t, [C.c_int32] * 3),
+    "riggs_node_mlp_backward_workspace_floats": (C.c_size_t, [C.c_int32] * 3),
+    "riggs_node_mlp_forward": (C.c_int, [C.POINTER(NodeMlp), C.c_int32, _P, _P, C.c_int32] + [_P] * 7),
+    "riggs_node_mlp_backward": (C.c_int, [C.POINTER(NodeMlp), C.c_int32] + [_P] * 7 + [C.POINTER(NodeMlpGrads), _P]),
 }
 
 

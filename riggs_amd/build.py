@@ -34,6 +34,7 @@ SOURCES = {
     "frame.hip": [],
     "densify.hip": ["-ffp-contract=off"],
     "node_reg.hip": ["-ffp-contract=off"],
+    "node_mlp.hip": ["-ffp-contract=off"],
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

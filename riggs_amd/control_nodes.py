@@ -9,8 +9,9 @@ kernel's neighbour lists) and ``skinning=True`` (softmax of a per-Gaussian (N, M
 (N, M) x (M, 14) product, left to the GEMM library) as the reference defines them; ``node_trans_bias`` (the GUI's drag-to-edit
 path, time_utils.py:1165-1213: an as-rigid-as-possible re-posing of the Gaussians around dragged nodes, under ``no_grad``) in
 torch ops on top of the kernel's blend — it runs per mouse event, not per training step.  The node network
-(``self.network``: nodes, t -> per-node attributes; 512-1024 rows, time_utils.py:990-1002) stays a torch module supplied by the
-caller — it is a few hundred rows through an MLP, not a per-Gaussian cost.  No CPU / eager fallback.
+(``self.network``: nodes, t -> per-node attributes; 512-1024 rows, time_utils.py:990-1002) is a torch module supplied by the
+caller: ``riggs_amd.node_network.DeformNetwork`` (csrc/node_mlp.hip) for the shipped flags, or any module ``(x, t) -> dict``.
+No CPU / eager fallback.
 """
 from __future__ import annotations
 
