@@ -547,6 +547,46 @@ int riggs_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* image, 
                            float* dL_dimage, riggs_stream stream);
 
 /* =====================================================================
+ * Optical-flow supervision of a stage-1 iteration (train_gui.py:1078-1121).
+ *
+ * Flow colours of gaussian_renderer.render_flow (gaussian_renderer/__init__.py:186-202), per Gaussian n:
+ *   p_k = xyz[n] + d_xyz_k[n],  h_k = [p_k, 1] . full_proj_k,  u_k = h_k.xyz / h_k.w  (plain division, no + 1e-7),
+ *   colour[n] = (u_2.x - u_1.x, u_2.y - u_1.y, motion_mask[n])
+ * xyz is a constant (the reference detaches it).  d_xyz1 / d_xyz2 (N, 3) may be NULL (a residual of 0.0).  full_proj1 /
+ * full_proj2 are DEVICE (4, 4) matrices in row-vector convention, the 16 floats the rasterizer reads as column-major
+ * (pass the same pointer twice when there is no second camera).  motion_mask[n] = sigmoid(mask_logit[n * mask_logit_stride])
+ * (the last column of the (N, fea_dim) feature: pointer to its first element, stride fea_dim), or 1 when mask_logit is NULL.
+ * backward recomputes the projections (nothing is saved) and writes dL/dd_xyz1, dL/dd_xyz2 (N, 3) and dL/dmask_logit (N,
+ * contiguous); each may be NULL.  A row whose incoming (dL/dcolour.x, dL/dcolour.y) is exactly zero gets exact zeros in both
+ * residual gradients, whatever its h.w (the reference yields 0 * inf = NaN at h.w = 0), and dL/dmask_logit is exactly zero
+ * where dL/dcolour.z is.  N = 0 is a no-op.
+ *
+ * Flow loss (train_gui.py:1101-1120), per pixel, image / gt (C, H, W), motion (3, H, W) (planes 0, 1 are read), alpha (H, W),
+ * flow (H, W, 2) in RAFT pixels (8-byte aligned), masks (H, W, mask_channels >= 2) (channels 0, 1 are read):
+ *   c = flow / (W, H) * 2;  live = alpha > 0.9 and (masks.0 > 0 or masks.1 > 0)
+ *   w = live * clamp(cos(|fid1 - fid2| pi / 2), 0.2, 1) * cos(mean_c |image - gt| pi / 2)
+ *   loss = mean over (H, W, 2) of |w c - w motion|
+ * fid1 / fid2: DEVICE scalars fid1_dev / fid2_dev, or, where that pointer is NULL, the float passed by value.  forward writes
+ * the loss (device scalar) and keeps w and the per-workgroup partial sums in `state` (riggs_flow_loss_state_floats floats);
+ * the partials are added in a fixed order (bitwise repeatable).  backward takes the upstream gradient as a DEVICE scalar and
+ * writes dL/dmotion (3, H, W), its third plane zero; a pixel with w = 0 gets exact zeros.
+ * ===================================================================== */
+int riggs_flow_colors_forward(int32_t N, const float* xyz, const float* d_xyz1, const float* d_xyz2, const float* full_proj1,
+                              const float* full_proj2, const float* mask_logit, int64_t mask_logit_stride, float* colour,
+                              riggs_stream stream);
+int riggs_flow_colors_backward(int32_t N, const float* xyz, const float* d_xyz1, const float* d_xyz2, const float* full_proj1,
+                               const float* full_proj2, const float* mask_logit, int64_t mask_logit_stride,
+                               const float* dL_dcolour, float* dL_dd_xyz1, float* dL_dd_xyz2, float* dL_dmask_logit,
+                               riggs_stream stream);
+size_t riggs_flow_loss_state_floats(int32_t H, int32_t W);
+int riggs_flow_loss_forward(int32_t C, int32_t H, int32_t W, int32_t mask_channels, const float* image, const float* gt,
+                            const float* motion, const float* alpha, const float* flow, const float* masks,
+                            const float* fid1_dev, const float* fid2_dev, float fid1, float fid2, float* state, float* loss,
+                            riggs_stream stream);
+int riggs_flow_loss_backward(int32_t H, int32_t W, const float* motion, const float* flow, const float* state,
+                             const float* g_loss, float* dL_dmotion, riggs_stream stream);
+
+/* =====================================================================
  * Skeleton projection loss: TrainRig.cal_skeleton_loss, train_rig.py:309-314, =
  * sampling_skeleton_points (:264-276) -> project_nodes_to_2d_elements (utils/other_utils.py:101-127) ->
  * pytorch3d.loss.chamfer_distance(x, y, norm=1) (third-party; restated from its published definition).

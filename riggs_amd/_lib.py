@@ -204,6 +204,11 @@ _SIGS = {
     "riggs_l1_ssim_state_floats": (C.c_size_t, [C.c_int32] * 3),
     "riggs_l1_ssim_forward": (C.c_int, [C.c_int32] * 3 + [_P, _P, C.c_float, _P, _P, _P]),
     "riggs_l1_ssim_backward": (C.c_int, [C.c_int32] * 3 + [_P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "riggs_flow_colors_forward": (C.c_int, [C.c_int32] + [_P] * 6 + [C.c_int64, _P, _P]),
+    "riggs_flow_colors_backward": (C.c_int, [C.c_int32] + [_P] * 6 + [C.c_int64] + [_P] * 5),
+    "riggs_flow_loss_state_floats": (C.c_size_t, [C.c_int32] * 2),
+    "riggs_flow_loss_forward": (C.c_int, [C.c_int32] * 4 + [_P] * 8 + [C.c_float] * 2 + [_P] * 3),
+    "riggs_flow_loss_backward": (C.c_int, [C.c_int32] * 2 + [_P] * 6),
     "riggs_cnode_backward_blocks": (C.c_int, [C.c_int32] * 3),
     "riggs_cnode_backward_workspace_floats": (C.c_size_t, [C.c_int32] * 4),
     "riggs_cnode_forward": (C.c_int, [C.c_int32] * 7 + [_P] * 17),

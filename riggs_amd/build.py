@@ -35,6 +35,7 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],
     "node_reg.hip": ["-ffp-contract=off"],
     "node_mlp.hip": ["-ffp-contract=off"],
+    "flow.hip": ["-ffp-contract=off"],  # (the loss forms fl(w c) - fl(w m) as the reference does: no fused multiply-subtract)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

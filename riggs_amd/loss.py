@@ -84,6 +84,102 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return l1_ssim(img1, img2)[1]
 
 
+# ---- optical-flow loss of a stage-1 iteration (train_gui.py:1101-1120) ------------------------------------------------------
+class _FlowLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, motion, image, gt, alpha, flow, masks, fid1, fid2):
+        _, H, W = motion.shape
+        lib = L.lib()
+        state = torch.empty(lib.riggs_flow_loss_state_floats(H, W), dtype=torch.float32, device=motion.device)
+        loss = torch.empty(1, dtype=torch.float32, device=motion.device)
+        t1, t2 = isinstance(fid1, torch.Tensor), isinstance(fid2, torch.Tensor)
+        L.check(lib.riggs_flow_loss_forward(image.shape[0], H, W, masks.shape[2], image.data_ptr(), gt.data_ptr(),
+                                            motion.data_ptr(), alpha.data_ptr(), flow.data_ptr(), masks.data_ptr(),
+                                            fid1.data_ptr() if t1 else None, fid2.data_ptr() if t2 else None,
+                                            0.0 if t1 else float(fid1), 0.0 if t2 else float(fid2), state.data_ptr(),
+                                            loss.data_ptr(), L.stream_ptr()), "riggs_flow_loss_forward")
+        ctx.save_for_backward(motion, flow, state)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        motion, flow, state = ctx.saved_tensors
+        _, H, W = motion.shape
+        g = torch.empty_like(motion)
+        g_loss = g_loss.to(torch.float32).contiguous()
+        L.check(L.lib().riggs_flow_loss_backward(H, W, motion.data_ptr(), flow.data_ptr(), state.data_ptr(), g_loss.data_ptr(),
+                                                 g.data_ptr(), L.stream_ptr()), "riggs_flow_loss_backward")
+        return (g,) + (None,) * 7
+
+
+def _fid(v, name, device):
+    if isinstance(v, torch.Tensor):
+        if v.numel() != 1:
+            raise L.RiggsHipError("%s must have one element" % name)
+        if not v.is_cuda:
+            return float(v)  # (a host tensor: read on the host, no device traffic)
+        return L.require_cuda_f32(name, v.detach()).reshape(1)
+    return float(v)
+
+
+def optical_flow_loss(image, gt_image, motion, alpha, flow, masks, fid1, fid2):
+    """The optical-flow term of a stage-1 iteration (train_gui.py:1101-1120) as one scalar tensor::
+
+        c    = flow / (W, H) * 2                                       # RAFT pixels -> NDC units
+        live = (alpha > 0.9) & ((masks[..., 0] > 0) | (masks[..., 1] > 0))
+        w    = live * clamp(cos(|fid1 - fid2| pi/2), 0.2, 1) * cos(mean_c |image - gt_image| pi/2)
+        loss = mean over (H, W, 2) of |w c - w motion[:2]|
+
+    ``motion`` is ``render_flow(...)["render"]`` (3, H, W) and the only differentiable input; ``image`` / ``gt_image`` are
+    (C, H, W), ``alpha`` is ``render_flow(...)["alpha"]`` ((1, H, W) or (H, W)), ``flow`` (h, w, 2), ``masks`` (h, w, >= 2).  A
+    flow file of another size is resampled by the reference's nearest-neighbour ``interpolate`` (a torch call, :1089-1091).
+    ``fid1`` / ``fid2``: 1-element device tensors (read on the device) or Python floats.  Two HIP launches forward, one
+    backward (csrc/flow.hip); the sum is formed in a fixed order, no call synchronises with the host."""
+    motion = L.require_cuda_f32("motion", motion)
+    if motion.dim() != 3 or motion.shape[0] != 3:
+        raise L.RiggsHipError("motion must be (3, H, W): render_flow(...)['render']")
+    _, H, W = motion.shape
+    image = _chw(image, "image").detach()
+    gt_image = _chw(gt_image, "gt_image").detach()
+    if image.shape != gt_image.shape or tuple(image.shape[1:]) != (H, W):
+        raise L.RiggsHipError("image and gt_image must be (C, %d, %d)" % (H, W))
+    alpha = L.require_cuda_f32("alpha", alpha.detach())
+    if alpha.numel() != H * W:
+        raise L.RiggsHipError("alpha must be (1, %d, %d)" % (H, W))
+    if flow.dim() != 3 or flow.shape[2] != 2 or masks.dim() != 3 or masks.shape[2] < 2:
+        raise L.RiggsHipError("flow must be (h, w, 2) and masks (h, w, C >= 2)")
+    if flow.shape[0] != H or flow.shape[1] != W:  # train_gui.py:1089-1091
+        flow = torch.nn.functional.interpolate(flow.permute([2, 0, 1])[None], (H, W))[0].permute(1, 2, 0)
+        masks = torch.nn.functional.interpolate(masks.permute([2, 0, 1])[None], (H, W))[0].permute(1, 2, 0)
+    flow = L.require_cuda_f32("flow", flow.detach(), (H, W, 2))
+    if flow.data_ptr() % 8:  # (a view at an odd offset: the kernels read (x, y) pairs)
+        flow = flow.clone()
+    masks = L.require_cuda_f32("masks", masks.detach(), (H, W, None))
+    return _FlowLoss.apply(motion, image, gt_image, alpha, flow, masks, _fid(fid1, "fid1", motion.device),
+                           _fid(fid2, "fid2", motion.device))
+
+
+def landmark_interpolate(landmarks, steps, step, interpolation='log'):
+    """The piecewise schedule of the trainer's loss weights (train_gui.py:63-81; ``lambda_optical`` at :1080): 0 before the
+    first step, the last landmark (at least 0) from the last step on, 0 on a segment that ends at a non-positive landmark,
+    else the log- or linear interpolation of the segment's two landmarks.  Host arithmetic only."""
+    import numpy as np
+    stage = int((step >= np.array(steps)).sum())
+    if stage == len(steps):
+        return max(0, landmarks[-1])
+    if stage == 0:
+        return 0
+    lo, hi = landmarks[stage - 1], landmarks[stage]
+    if hi <= 0:
+        return 0
+    ratio = (step - steps[stage - 1]) / (steps[stage] - steps[stage - 1])
+    if interpolation == 'log':
+        return np.exp(np.log(lo) * (1 - ratio) + np.log(hi) * ratio)
+    if interpolation == 'linear':
+        return lo * (1 - ratio) + hi * ratio
+    raise NotImplementedError("unknown interpolation type: %s" % interpolation)
+
+
 # ---- skeleton projection loss (train_rig.py:309-314) ---------------------------------------------------------------------
 class _SkeletonProjection(torch.autograd.Function):
     @staticmethod

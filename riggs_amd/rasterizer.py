@@ -373,11 +373,11 @@ def _backward_workspace(nbytes: int, dev, N: int) -> torch.Tensor:
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, arena=None):
         ctx.set_materialize_grads(False)
         color, radii, depth, alpha, s = rasterize_forward(settings, means3D, sh, colors_precomp, opacities, scales,
-                                                          rotations, cov3Ds_precomp)
-        ctx.s = s
+                                                          rotations, cov3Ds_precomp, arena=arena)
+        ctx.s, ctx.arena = s, arena
         ctx.save_for_backward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.mark_non_differentiable(radii)
         return color, radii, depth, alpha
@@ -385,10 +385,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
+        if ctx.arena is not None:
+            ctx.arena.resolve(block=False)  # raises if the forward of this frame is known to have overflowed
         g = rasterize_backward(ctx.s, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, None,
                                None, grad_color, grad_depth, grad_alpha)
         g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, _ = g
-        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, None
+        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, None, None
 
 
 def _prep(name, t, shape):
@@ -398,9 +400,12 @@ def _prep(name, t, shape):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, arena: Optional[RasterArena] = None):
+        """``arena`` (an addition to upstream's signature): a persistent ``RasterArena``; from its second frame on the instance
+        count stays on the device (no host read per call), which a captured iteration needs."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.arena = arena
 
     def markVisible(self, positions):
         """Frustum test of upstream's markVisible: view-space z > 0.2."""
@@ -427,7 +432,7 @@ class GaussianRasterizer(nn.Module):
         rotations = L.require_cuda_f32("rotations", rotations, (N, 4)) if rotations is not None else None
         cov3D_precomp = L.require_cuda_f32("cov3D_precomp", cov3D_precomp, (N, 6)) if cov3D_precomp is not None else None
         return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                         cov3D_precomp, self.raster_settings)
+                                         cov3D_precomp, self.raster_settings, self.arena)
 
 
 # ---- debugging / test access to the opaque arenas --------------------------------------

@@ -206,6 +206,122 @@ def render(viewpoint_camera, pc, pipe, bg_color, d_xyz, d_rotation, d_scaling, d
             "depth": depth, "alpha": alpha, "bg_color": bg}
 
 
+class _FlowColors(torch.autograd.Function):
+    """The per-Gaussian flow colours of ``render_flow`` as ONE autograd node (csrc/flow.hip): a launch forward, a launch
+    backward that recomputes both projections."""
+
+    @staticmethod
+    def forward(ctx, xyz, d_xyz1, d_xyz2, logit, proj1, proj2):
+        N = xyz.shape[0]
+        colour = torch.empty(N, 3, dtype=torch.float32, device=xyz.device)
+        stride = 0 if logit is None else logit.stride(0)
+        L.check(L.lib().riggs_flow_colors_forward(N, xyz.data_ptr(), L.ptr(d_xyz1), L.ptr(d_xyz2), proj1.data_ptr(),
+                                                  proj2.data_ptr(), L.ptr(logit), stride, colour.data_ptr(), L.stream_ptr()),
+                "riggs_flow_colors_forward")
+        ctx.save_for_backward(xyz, d_xyz1, d_xyz2, logit, proj1, proj2)
+        ctx.set_materialize_grads(False)
+        return colour
+
+    @staticmethod
+    def backward(ctx, g_colour):
+        xyz, d_xyz1, d_xyz2, logit, proj1, proj2 = ctx.saved_tensors
+        if g_colour is None:
+            return (None,) * 6
+        N = xyz.shape[0]
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=xyz.device)  # noqa: E731
+        g1 = new(N, 3) if (d_xyz1 is not None and need[1]) else None
+        g2 = new(N, 3) if (d_xyz2 is not None and need[2]) else None
+        gl = new(N) if (logit is not None and need[3]) else None
+        if g1 is None and g2 is None and gl is None:
+            return (None,) * 6
+        g_colour = L.require_cuda_f32("dL/dcolour", g_colour, (N, 3))
+        stride = 0 if logit is None else logit.stride(0)
+        L.check(L.lib().riggs_flow_colors_backward(N, xyz.data_ptr(), L.ptr(d_xyz1), L.ptr(d_xyz2), proj1.data_ptr(),
+                                                   proj2.data_ptr(), L.ptr(logit), stride, g_colour.data_ptr(), L.ptr(g1),
+                                                   L.ptr(g2), L.ptr(gl), L.stream_ptr()), "riggs_flow_colors_backward")
+        return None, g1, g2, gl, None, None
+
+
+def flow_colors(pc, viewpoint_camera1, viewpoint_camera2, d_xyz1, d_xyz2):
+    """``colors_precomp`` of ``render_flow`` (gaussian_renderer/__init__.py:186-202), (N, 3): the screen-space motion of every
+    Gaussian between ``xyz + d_xyz1`` seen by camera 1 and ``xyz + d_xyz2`` seen by camera 2 (camera 1 when None) in its first
+    two columns — ``u = ([p, 1] @ full_proj_transform)``, ``u.xy / u.w`` with the plain division of the reference — and
+    ``pc.motion_mask`` in the third.  ``_xyz`` is a constant here, as in the reference; either residual may be ``0.0``.
+    Differentiable w.r.t. the residuals and ``pc.feature[:, -1]``.  A residual is an (N, 3) tensor or the float ``0.0`` (what the
+    trainer passes); another scalar or a broadcastable shape, which the reference's ``xyz + d_xyz`` would take, is refused.
+
+    Deviation from the reference, on purpose: a Gaussian whose incoming colour gradient is exactly zero (culled, or it reached
+    no pixel: most Gaussians of a frame) receives exact zeros in both residual gradients, also when its ``u.w`` is 0 — the
+    reference's autograd forms 0 * inf = NaN there."""
+    xyz = L.require_cuda_f32("_xyz", pc.get_xyz.detach(), (None, 3))
+    N = xyz.shape[0]
+    for name, d in (("d_xyz1", d_xyz1), ("d_xyz2", d_xyz2)):
+        if not isinstance(d, torch.Tensor) and not _is_zero_scalar(d):
+            raise L.RiggsHipError("%s must be an (N, 3) tensor or the float 0.0" % name)
+    d1 = None if _is_zero_scalar(d_xyz1) else L.require_cuda_f32("d_xyz1", d_xyz1, (N, 3))
+    d2 = None if _is_zero_scalar(d_xyz2) else L.require_cuda_f32("d_xyz2", d_xyz2, (N, 3))
+    cam2 = viewpoint_camera2 if viewpoint_camera2 is not None else viewpoint_camera1
+    proj1 = L.require_cuda_f32("full_proj_transform", viewpoint_camera1.full_proj_transform, (4, 4))
+    proj2 = L.require_cuda_f32("full_proj_transform", cam2.full_proj_transform, (4, 4))
+    logit = None
+    if getattr(pc, "with_motion_mask", False):
+        feature = pc.feature
+        if not feature.is_cuda or feature.dtype is not torch.float32 or feature.dim() != 2 or feature.shape[0] != N:
+            raise L.RiggsHipError("pc.feature must be a CUDA(HIP) float32 (N, fea_dim) tensor")
+        logit = feature[:, -1]  # (a strided view: the kernel reads the column in place)
+    return _FlowColors.apply(xyz, d1, d2, logit, proj1, proj2)
+
+
+_ZERO_BG = {}
+
+
+def render_flow(pc, viewpoint_camera1, viewpoint_camera2, d_xyz1, d_xyz2, d_rotation1, d_scaling1, scaling_modifier=1.0,
+                compute_cov3D_python=False, scale_const=None, d_rot_as_res=True, arena: RasterArena = None, **kwargs):
+    """Same contract as the reference ``render_flow`` (gaussian_renderer/__init__.py:154-269; returns the same dict): the
+    Gaussians at time 1 rasterized from camera 1 with the colours of ``flow_colors`` — channels 0, 1 of ``render`` are the
+    rendered screen-space motion towards (camera 2, time 2), channel 2 the rendered motion mask — over a zero background.
+
+    The glue is ``render_flow``'s, not ``render``'s: ``rotations = get_rotation + d_rotation1`` (normalised before the add,
+    not after), ``scales = get_scaling + d_scaling1``, ``scale_const`` replaces the scales, ``d_rot_as_res=False`` composes by
+    ``quaternion_multiply``, ``compute_cov3D_python`` goes through ``get_covariance``.  The colours are one HIP node, the
+    rasterizer is the drop-in one; ``arena`` (an addition, as in ``render``) keeps the instance count on the device, which a
+    captured iteration needs."""
+    xyz = pc.get_xyz
+    colour = flow_colors(pc, viewpoint_camera1, viewpoint_camera2, d_xyz1, d_xyz2)
+    bg = _ZERO_BG.get(xyz.device)
+    if bg is None:
+        bg = _ZERO_BG[xyz.device] = torch.zeros(3, dtype=torch.float32, device=xyz.device)
+    settings = GaussianRasterizationSettings(
+        image_height=int(viewpoint_camera1.image_height), image_width=int(viewpoint_camera1.image_width),
+        tanfovx=math.tan(viewpoint_camera1.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera1.FoVy * 0.5), bg=bg,
+        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera1.world_view_transform,
+        projmatrix=viewpoint_camera1.full_proj_transform, sh_degree=0, campos=viewpoint_camera1.camera_center,
+        prefiltered=False, debug=False)
+    screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0  # non-leaf, as the reference builds it
+    if screenspace_points.requires_grad:  # (not under no_grad: the reference swallows the error there, :176-179)
+        screenspace_points.retain_grad()
+    means3D = xyz + d_xyz1
+    opacity = pc.get_opacity
+
+    def rotated():  # :228-231, :243-246
+        if d_rot_as_res:
+            return pc.get_rotation + d_rotation1
+        return pc.get_rotation if type(d_rotation1) is float else quaternion_multiply(d_rotation1, pc.get_rotation)
+    scales = rotations = cov3D_precomp = None
+    if scale_const is not None:
+        scales, rotations = torch.ones_like(pc.get_scaling) * scale_const, rotated()
+    elif compute_cov3D_python:
+        cov3D_precomp = pc.get_covariance(scaling_modifier, d_rotation=None if type(d_rotation1) is float else d_rotation1)
+    else:
+        scales, rotations = pc.get_scaling + d_scaling1, rotated()
+    image, radii, depth, alpha = GaussianRasterizer(raster_settings=settings, arena=arena)(
+        means3D=means3D, means2D=screenspace_points, shs=None, colors_precomp=colour, opacities=opacity, scales=scales,
+        rotations=rotations, cov3D_precomp=cov3D_precomp)
+    return {"render": image, "depth": depth, "alpha": alpha, "viewspace_points": screenspace_points,
+            "visibility_filter": radii > 0, "radii": radii}
+
+
 def _general_opacity(pc, d_opacity, constant_scale):
     """gaussian_renderer/__init__.py:76-82: opaque splats when a constant scale is forced, else sigmoid(_opacity) (+ residual)."""
     base = pc.get_opacity
