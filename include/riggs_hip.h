@@ -220,6 +220,29 @@ int riggs_raster_backward_workspace_rows(int32_t num_points, size_t* offset, siz
  * their offsets]; need not be zeroed */
 size_t riggs_raster_backward_workspace_bytes_ordered(int32_t num_points, int64_t instance_capacity);
 
+/* A second colour set over a rendered frame's tile lists.  Replaces the SECOND render() of the same camera and geometry that
+ * differs only in the per-Gaussian colour: the motion-mask render of train_gui.py:1123-1130 (render_motion=True, every geometry
+ * input detached, colours [m, 0, 1-m]: gaussian_renderer/__init__.py:94-98), render_rig.py:152-160 (override_color=skinning_color).
+ * `geom`, `binning`, `image_state`, `counters` are those of a frame after riggs_raster_render — all READ ONLY here, so the frame's
+ * own riggs_raster_backward may run before or after; cfg gives num_points, image_height, image_width (and debug), the rest of it is
+ * not read.  No preprocess, no sort, no binning: per pixel
+ *   out[ch] = sum_i colors[i][ch] alpha_i T_i + final_T bg[ch]
+ * over the instances of the pixel's tile list in front of its n_contrib — the set the frame's forward composited —, with the alpha
+ * evaluation of the compositing backward.  `bg` is this call's own and need not be the frame's.
+ * The backward is the colour gradient only, dL/dcolors[n][ch] = sum_pix alpha T dL_dcolor[ch][pix] (float atomics, one triple per
+ * contributing (instance, tile)); it zero-fills dL_dcolors itself on the stream, so the buffer is fully written.
+ * counters != NULL: when the frame's overflow flag (counters[1]) is set the forward writes a ZERO image and the backward ZERO
+ * gradients, decided on the device (as riggs_raster_backward); NULL skips the guard.  num_points == 0 is valid: the image is bg.
+ * Neither call allocates, reads back or synchronises (cfg.debug: synchronises and checks): both are legal inside a stream capture.
+ * (Added symbols do not change riggs_version(): the ABI only grows; a caller that needs them resolves them by name.) */
+int riggs_raster_recolor_forward(const riggs_raster_cfg* cfg /* N, H, W */, const void* geom, const void* binning,
+                                 int64_t instance_capacity, const void* image_state, const uint32_t* counters /* NULL: no guard */,
+                                 const float* colors /*(N,3)*/, const float* bg /*(3,)*/, float* out_color /*(3,H,W)*/,
+                                 riggs_stream stream);
+int riggs_raster_recolor_backward(const riggs_raster_cfg* cfg, const void* geom, const void* binning, int64_t instance_capacity,
+                                  const void* image_state, const uint32_t* counters, const float* dL_dcolor /*(3,H,W)*/,
+                                  float* dL_dcolors /*(N,3), fully written*/, riggs_stream stream);
+
 /* =====================================================================
  * Skeleton deformation.  Replaces the torch-op graph of
  *   SkeletonWarp.deform_by_pose  skeleton_utils/skeleton_warp.py:130-172
@@ -610,6 +633,19 @@ int riggs_skeleton_projection_backward(int32_t J, int32_t S, int32_t M, const in
                                        float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
                                        float* state, const float* g_loss, const float* g_weighted, float* grad_nodes,
                                        riggs_stream stream);
+/* The node projection term of stage 1 (train_gui.py:1133-1139): the point set is the J >= 1 rows of d_nodes themselves (the
+ * control nodes: no bones, no sampling), projected by project_nodes_to_2d_elements and compared with `thinned` (M, 2) by the same
+ * two-sided L1 chamfer distance (mean over the points of each side, summed).  Kernels of its own: the entry points above compute
+ * what they always did.  Arguments as above; `state` holds riggs_node_projection_state_floats(J, M) floats, 8-byte aligned.
+ * Deterministic. */
+size_t riggs_node_projection_state_floats(int32_t J, int32_t M);
+int riggs_node_projection_forward(int32_t J, int32_t M, const float* d_nodes, const float* world_view_transform, float fx, float fy,
+                                  float cx, float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
+                                  float* state, float* loss2, riggs_stream stream);
+int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, const float* world_view_transform, float fx, float fy,
+                                   float cx, float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
+                                   float* state, const float* g_loss, const float* g_weighted, float* grad_nodes,
+                                   riggs_stream stream);
 
 /* =====================================================================
  * Stage-1 control-node deformation, per-Gaussian part: ControlNodeWarp.cal_nn_weight

@@ -169,6 +169,8 @@ _SIGS = {
     "riggs_raster_render": (C.c_int, [C.POINTER(RasterCfg), _P, _P, C.c_int64, C.c_size_t, _P, _P, _P, _P, _P, _P]),
     "riggs_raster_backward": (C.c_int, [C.POINTER(RasterCfg)] + [_P] * 11 + [_P, _P, _P, C.c_int64, _P, _P] + [_P] * 3
                               + [_P] + [_P] * 10 + [_P]),
+    "riggs_raster_recolor_forward": (C.c_int, [C.POINTER(RasterCfg), _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "riggs_raster_recolor_backward": (C.c_int, [C.POINTER(RasterCfg), _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "riggs_fk_forward": (C.c_int, [C.c_int32] + [_P] * 8),
     "riggs_fk_backward": (C.c_int, [C.c_int32] + [_P] * 8),
     "riggs_lbs_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_P] * 15),
@@ -216,6 +218,9 @@ _SIGS = {
     "riggs_skeleton_projection_state_floats": (C.c_size_t, [C.c_int32] * 3),
     "riggs_skeleton_projection_forward": (C.c_int, [C.c_int32] * 3 + [_P] * 4 + [C.c_float] * 4 + [_P] * 6),
     "riggs_skeleton_projection_backward": (C.c_int, [C.c_int32] * 3 + [_P] * 4 + [C.c_float] * 4 + [_P] * 8),
+    "riggs_node_projection_state_floats": (C.c_size_t, [C.c_int32] * 2),
+    "riggs_node_projection_forward": (C.c_int, [C.c_int32] * 2 + [_P] * 2 + [C.c_float] * 4 + [_P] * 6),
+    "riggs_node_projection_backward": (C.c_int, [C.c_int32] * 2 + [_P] * 2 + [C.c_float] * 4 + [_P] * 8),
     "riggs_raster_set_trace": (C.c_int, [_P]),
     "riggs_raster_set_trace_items": (C.c_int, [C.c_uint64]),
     "riggs_mlp_forward": (C.c_int, [C.c_int32] * 5 + [_P] * 10 + [C.c_int32, _P]),

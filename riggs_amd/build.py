@@ -19,6 +19,7 @@ TORCH_SRC = os.path.join(HERE, "csrc_torch", "riggs_torch.cpp")
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=fast"],
+    "recolor.hip": ["-ffp-contract=fast"],  # (its alpha evaluation is render.hip's: the same contraction)
     "binning.hip": ["-ffp-contract=off"],  # (hosts color_job.h: the same colours, bit for bit, as preprocess.hip)
     "deform.hip": ["-ffp-contract=fast"],
     "knn.hip": ["-ffp-contract=fast"],

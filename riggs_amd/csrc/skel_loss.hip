@@ -209,6 +209,108 @@ static int skel_fill(SkelProjArgs& a, int J, int S, int M, const int32_t* parent
   return 0;
 }
 
+
+// ---- node projection term of stage 1 (/root/reference/train_gui.py:1133-1139) -------------------------------------------------
+// The point set is the J control nodes themselves: no bones, no sampling steps (P = J).  Kernels and entry points of its own —
+// everything above is the bone form, untouched — that share the argument block (parents, t unused; S = 1), the key format,
+// `skel_pixels` and `skel_finish_kernel` (which only sees P, M and the keys).
+__device__ __forceinline__ void node_point(const SkelProjArgs& a, int p, float& tx, float& ty, float& tz) {
+  const float px = a.nodes[3 * p + 0], py = a.nodes[3 * p + 1], pz = a.nodes[3 * p + 2];
+  const float* V = a.view;
+  tx = px * V[0] + py * V[4] + pz * V[8] + V[12];
+  ty = px * V[1] + py * V[5] + pz * V[9] + V[13];
+  tz = px * V[2] + py * V[6] + pz * V[10] + V[14];
+}
+__device__ __forceinline__ float2 node_project(const SkelProjArgs& a, int p) {
+  float tx, ty, tz;
+  node_point(a, p, tx, ty, tz);
+  return make_float2(a.fy * ty / tz + a.cy, a.fx * tx / tz + a.cx);
+}
+
+// all-pairs nearest neighbours, both directions in one grid: the shape of skel_nearest_kernel over the nodes' projections
+__global__ void __launch_bounds__(SKEL_Q) node_nearest_kernel(SkelProjArgs a, int n_xblocks, int n_yslices_of_x) {
+  __shared__ float2 s_c[SKEL_C];
+  const bool xdir = (int)blockIdx.x < n_xblocks;  // queries = nodes, candidates = pixels
+  int qb, cs;
+  if (xdir) { qb = blockIdx.x / n_yslices_of_x; cs = blockIdx.x - qb * n_yslices_of_x; }
+  else {
+    const int r = blockIdx.x - n_xblocks, n_slices = (a.P + SKEL_C - 1) / SKEL_C;
+    qb = r / n_slices; cs = r - qb * n_slices;
+  }
+  const int M = skel_pixels(a);
+  const int nq = xdir ? a.P : M, nc = xdir ? M : a.P;
+  const int i = qb * SKEL_Q + threadIdx.x;
+  const int base = cs * SKEL_C, n = min(SKEL_C, nc - base);
+  if (n <= 0 || qb * SKEL_Q >= nq) return;  // beyond the frame's pixel count (the grid is sized for the capacity)
+  const float2* pix = reinterpret_cast<const float2*>(a.thinned);
+  for (int j = threadIdx.x; j < n; j += SKEL_Q) s_c[j] = xdir ? pix[base + j] : node_project(a, base + j);
+  float2 me = make_float2(0.f, 0.f);
+  if (i < nq) me = xdir ? node_project(a, i) : pix[i];
+  __syncthreads();
+  float best = 3.0e38f;
+  int bj = 0;
+#pragma unroll 8
+  for (int j = 0; j < n; ++j) {
+    const float2 o = s_c[j];
+    const float d = fabsf(me.x - o.x) + fabsf(me.y - o.y);
+    if (d < best) { best = d; bj = j; }
+  }
+  if (i < nq) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)(base + bj);
+    atomicMax((xdir ? a.near_x : a.near_y) + i, ~key);
+  }
+}
+
+// One workgroup per node: the pulls of the pixels that chose it (integer counters in LDS: exact under any order), then its own
+// nearest pixel, back through the pinhole and the view transform.  Deterministic.
+__global__ void __launch_bounds__(256) node_grad_kernel(SkelProjArgs a, const float* g_loss, const float* g_weighted, const float* weight,
+                                                        float* grad_nodes) {
+  __shared__ int s_pull[2];
+  const int j = blockIdx.x;
+  if (threadIdx.x < 2) s_pull[threadIdx.x] = 0;
+  __syncthreads();
+  const int M = skel_pixels(a);
+  float tx, ty, tz;
+  node_point(a, j, tx, ty, tz);
+  const float py = a.fy * ty / tz + a.cy, px = a.fx * tx / tz + a.cx;
+  int cy_ = 0, cx_ = 0;
+  for (int m = threadIdx.x; m < M; m += 256) {
+    if ((int)(unsigned)(~a.near_y[m]) != j) continue;
+    cy_ += (int)sgn(py - a.thinned[2 * m + 0]);
+    cx_ += (int)sgn(px - a.thinned[2 * m + 1]);
+  }
+  if (cy_) atomicAdd(&s_pull[0], cy_);
+  if (cx_) atomicAdd(&s_pull[1], cx_);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const float g = (g_loss ? g_loss[0] : 0.f) + (g_weighted ? g_weighted[0] * (weight ? weight[0] : 1.f) : 0.f);
+  const float wx = g / (float)a.P, wy = g / (float)M;
+  const int ix = (int)(unsigned)(~a.near_x[j]);
+  const float gy = wx * sgn(py - a.thinned[2 * ix + 0]) + wy * (float)s_pull[0];
+  const float gx = wx * sgn(px - a.thinned[2 * ix + 1]) + wy * (float)s_pull[1];
+  const float iz = 1.0f / tz;
+  const float gtx = gx * a.fx * iz, gty = gy * a.fy * iz;
+  const float gtz = -(gy * a.fy * ty + gx * a.fx * tx) * iz * iz;
+  const float* V = a.view;
+  grad_nodes[3 * j + 0] = gtx * V[0] + gty * V[1] + gtz * V[2];
+  grad_nodes[3 * j + 1] = gtx * V[4] + gty * V[5] + gtz * V[6];
+  grad_nodes[3 * j + 2] = gtx * V[8] + gty * V[9] + gtz * V[10];
+}
+
+static int node_fill(SkelProjArgs& a, int J, int M, const float* d_nodes, const float* view, float fx, float fy, float cx, float cy,
+                     const float* thinned, const int32_t* pixel_count, float* state) {
+  RIGGS_REQUIRE(J >= 1 && J < (1 << 30) && M >= 1 && M < (1 << 30), "empty or oversized point set");
+  RIGGS_REQUIRE(d_nodes && view && thinned && state, "NULL buffer");
+  RIGGS_REQUIRE(((uintptr_t)state & 7) == 0, "state must be 8-byte aligned");
+  memset(&a, 0, sizeof(a));
+  a.J = J; a.S = 1; a.M = M; a.P = J;
+  a.nodes = d_nodes; a.view = view;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.thinned = thinned; a.m_dev = pixel_count;
+  a.near_x = (unsigned long long*)state;
+  a.near_y = (unsigned long long*)(state + 2 * (size_t)J);
+  return 0;
+}
+
 }  // namespace riggs
 
 using namespace riggs;
@@ -249,6 +351,40 @@ int riggs_skeleton_projection_backward(int32_t J, int32_t S, int32_t M, const in
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(skel_bone_grad_kernel, dim3(J - 1), dim3(256), 0, s, a, g_loss, g_weighted, weight);
   hipLaunchKernelGGL(skel_joint_gather_kernel, dim3(1), dim3(256), 0, s, a, grad_nodes);
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+size_t riggs_node_projection_state_floats(int32_t J, int32_t M) {
+  if (J < 1 || M < 0) return 0;
+  return 2 * (size_t)J + 2 * (size_t)M;
+}
+
+int riggs_node_projection_forward(int32_t J, int32_t M, const float* d_nodes, const float* world_view_transform, float fx, float fy,
+                                  float cx, float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
+                                  float* state, float* loss2, riggs_stream stream) {
+  SkelProjArgs a;
+  if (int rc = node_fill(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  RIGGS_REQUIRE(loss2, "NULL buffer");
+  hipStream_t s = (hipStream_t)stream;
+  RIGGS_HIP_CHECK(hipMemsetAsync(state, 0, sizeof(float) * (2 * (size_t)J + 2 * (size_t)M), s));  // zero = "no neighbour yet"
+  const int ysl = (M + SKEL_C - 1) / SKEL_C, xsl = (J + SKEL_C - 1) / SKEL_C;
+  const int n_xblocks = ((J + SKEL_Q - 1) / SKEL_Q) * ysl, n_yblocks = ((M + SKEL_Q - 1) / SKEL_Q) * xsl;
+  hipLaunchKernelGGL(node_nearest_kernel, dim3(n_xblocks + n_yblocks), dim3(SKEL_Q), 0, s, a, n_xblocks, ysl);
+  hipLaunchKernelGGL(skel_finish_kernel, dim3(1), dim3(1024), 0, s, a, weight, loss2);
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, const float* world_view_transform, float fx, float fy,
+                                   float cx, float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
+                                   float* state, const float* g_loss, const float* g_weighted, float* grad_nodes,
+                                   riggs_stream stream) {
+  SkelProjArgs a;
+  if (int rc = node_fill(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  RIGGS_REQUIRE((g_loss || g_weighted) && grad_nodes, "NULL buffer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(node_grad_kernel, dim3(J), dim3(256), 0, s, a, g_loss, g_weighted, weight, grad_nodes);
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
 }

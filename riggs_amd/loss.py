@@ -78,6 +78,19 @@ def l1_loss(network_output, gt):
     return l1_ssim(network_output, gt)[0]
 
 
+def motion_mask_loss(gt_alpha_mask, motion_image):
+    """The motion-mask term of a stage-1 iteration (train_gui.py:1129): ``l1_loss(gt_alpha_mask, motion_image)`` for the
+    (1, H, W) mask against the (H, W) first channel of the motion render (``render(..., render_motion=True)["render"][0]``) —
+    ``mean |mask - motion|`` on the fused L1 kernel with the plane viewed as one channel; differentiable w.r.t.
+    ``motion_image``."""
+    plane = lambda t: t[None] if t.dim() == 2 else t  # noqa: E731
+    motion, mask = plane(motion_image), plane(gt_alpha_mask)
+    if motion.dim() != 3 or motion.shape[0] != 1 or mask.shape != motion.shape:
+        raise L.RiggsHipError("motion_mask_loss takes a (1, H, W) mask and an (H, W) plane, got %s and %s"
+                              % (tuple(gt_alpha_mask.shape), tuple(motion_image.shape)))
+    return _L1SSIM.apply(_chw(motion, "motion_image"), _chw(mask, "gt_alpha_mask").detach())[0]
+
+
 def ssim(img1, img2, window_size=11, size_average=True):
     if window_size != 11 or not size_average:
         raise NotImplementedError("the HIP kernel implements the trainer's call: window_size=11, size_average=True")
@@ -269,6 +282,63 @@ def cal_skeleton_loss(d_nodes, parents, viewpoint_cam, t=None, num_sample=512, w
             raise L.RiggsHipError("pixel_count must be a CUDA(HIP) int32 scalar tensor")
         pixel_count = pixel_count.reshape(1)
     loss, weighted = _SkeletonProjection.apply(d_nodes, par, t, view, thinned, weight, pixel_count, fx, fy, cx, cy)
+    return loss if weight is None else (loss, weighted)
+
+
+class _NodeProjection(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d_nodes, view, thinned, weight, count, fx, fy, cx, cy):
+        J, M = d_nodes.shape[0], thinned.shape[0]
+        lib = L.lib()
+        n_state = lib.riggs_node_projection_state_floats(J, M)
+        state = torch.empty(max(int(n_state), 2) // 2 + 1, dtype=torch.float64, device=d_nodes.device)  # 8-byte aligned
+        loss2 = torch.empty(2, dtype=torch.float32, device=d_nodes.device)
+        L.check(lib.riggs_node_projection_forward(J, M, d_nodes.data_ptr(), view.data_ptr(), fx, fy, cx, cy, thinned.data_ptr(),
+                                                  L.ptr(count), L.ptr(weight), state.data_ptr(), loss2.data_ptr(), L.stream_ptr()),
+                "riggs_node_projection_forward")
+        ctx.save_for_backward(d_nodes, view, thinned, state, weight, count)
+        ctx.intr = (fx, fy, cx, cy)
+        ctx.set_materialize_grads(False)
+        return loss2[0], loss2[1]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_weighted):
+        d_nodes, view, thinned, state, weight, count = ctx.saved_tensors
+        if g_loss is None and g_weighted is None:
+            return (None,) * 9
+        f = lambda g: None if g is None else g.to(torch.float32).contiguous()  # noqa: E731
+        g_loss, g_weighted = f(g_loss), f(g_weighted)
+        grad = torch.empty_like(d_nodes)
+        fx, fy, cx, cy = ctx.intr
+        L.check(L.lib().riggs_node_projection_backward(d_nodes.shape[0], thinned.shape[0], d_nodes.data_ptr(), view.data_ptr(), fx, fy,
+                                                       cx, cy, thinned.data_ptr(), L.ptr(count), L.ptr(weight), state.data_ptr(),
+                                                       L.ptr(g_loss), L.ptr(g_weighted), grad.data_ptr(), L.stream_ptr()),
+                "riggs_node_projection_backward")
+        return (grad,) + (None,) * 8
+
+
+def node_projection_loss(d_nodes, viewpoint_cam, weight=None, pixel_count=None):
+    """The node projection term of a stage-1 iteration (/root/reference/train_gui.py:1134-1138): all M control nodes
+    projected by ``project_nodes_to_2d_elements`` (utils/other_utils.py:101-127: elements are (row, col), ``K``'s principal
+    point when the camera has one) against ``viewpoint_cam.thinned`` by the two-sided L1 chamfer distance with pytorch3d's
+    default reductions (mean over the points of each side, summed); differentiable w.r.t. ``d_nodes``.  Kernels of its own next
+    to the skeleton-projection ones (csrc/skel_loss.hip: the point set is the nodes themselves, no parents, no sampling steps).
+    ``weight`` / ``pixel_count``: the contract of ``cal_skeleton_loss`` — with ``weight`` the pair ``(loss, weight * loss)``."""
+    d_nodes = L.require_cuda_f32("d_nodes", d_nodes).contiguous()
+    if d_nodes.dim() != 2 or d_nodes.shape[1] != 3 or d_nodes.shape[0] < 1:
+        raise L.RiggsHipError("d_nodes must be (M >= 1, 3)")
+    thinned = L.require_cuda_f32("viewpoint_cam.thinned", viewpoint_cam.thinned).contiguous()
+    if thinned.dim() != 2 or thinned.shape[1] != 2 or thinned.shape[0] == 0:
+        raise L.RiggsHipError("viewpoint_cam.thinned must be (P >= 1, 2) (row, col)")
+    view = L.require_cuda_f32("viewpoint_cam.world_view_transform", viewpoint_cam.world_view_transform, (4, 4)).contiguous()
+    fx, fy, cx, cy = camera_intrinsics(viewpoint_cam)
+    if weight is not None:
+        weight = L.require_cuda_f32("weight", weight).reshape(1)
+    if pixel_count is not None:
+        if not pixel_count.is_cuda or pixel_count.dtype != torch.int32:
+            raise L.RiggsHipError("pixel_count must be a CUDA(HIP) int32 scalar tensor")
+        pixel_count = pixel_count.reshape(1)
+    loss, weighted = _NodeProjection.apply(d_nodes, view, thinned, weight, pixel_count, fx, fy, cx, cy)
     return loss if weight is None else (loss, weighted)
 
 

@@ -63,6 +63,11 @@ class RasterArena:
         # is the frame's persistent state — instead of being a module-wide switch toggled around the capture.
         self.sparse_grad_rows = False
         self._layout_key = None  # (capacity, N, H, W) the arena's walk history belongs to
+        # frames rendered through this arena so far: a saved state remembers the value its frame left, and ``recolor_forward`` /
+        # ``recolor_backward`` refuse a state whose arena has rendered since (the binning buffer holds the later frame's lists).
+        # Counted where Python asks for the frame's buffer (``ensure``): a REPLAY of a captured hipGraph that renders through the
+        # arena is not seen, so lists kept from an eager frame must not be used across replays of a graph that shares the arena
+        self.frames = 0
 
     def _post(self, counters: torch.Tensor, cap: int):
         """Queue an asynchronous read-back of (R, overflow) behind the frame just launched."""
@@ -102,12 +107,14 @@ class RasterArena:
                                   "outputs are invalid.  The arena is regrown on the next call." % (R, cap))
         return True
 
-    def ensure(self, cap: int, N: int, H: int, W: int, device, minimum: Optional[int] = None):
+    def ensure(self, cap: int, N: int, H: int, W: int, device, minimum: Optional[int] = None, frame: bool = True):
         """The arena for ``cap`` instances (the previous frame's count with the growth head-room).  An arena that still holds
         ``minimum`` (the count with a THIRD of that head-room; default: ``cap``) is kept: a scene whose count creeps up from
         frame to frame — every training iteration — would otherwise be given a new arena, and a fresh walk history, by each
         frame, including the one a hipGraph capture records (the allocation and the history's memset then replay for ever)."""
         cap = max(int(cap), self.min_capacity)
+        if frame:  # (every frame through the arena asks for its buffer here; ``top_up`` renders nothing)
+            self.frames += 1
         self._dims = (N, H, W, device)
         same = self.binning is not None and self.binning.device == device
         if same and (cap if minimum is None else min(int(minimum), cap)) <= self.capacity:
@@ -131,7 +138,7 @@ class RasterArena:
         """Full head-room over the last frame's count, now (eagerly): what the owner of a hipGraph capture calls between its
         warm-up frames and the capture, so that the captured frame neither allocates nor resets the history."""
         if self._dims is not None and self.last_R >= 0:
-            self.ensure(int(self.last_R * self.growth) + 1, *self._dims)
+            self.ensure(int(self.last_R * self.growth) + 1, *self._dims, frame=False)
 
     def _with_fresh_history(self, N: int, H: int, W: int):
         """The arena's one piece of frame-to-frame state — how deep the forward walked every tile's list — sits at an offset
@@ -243,6 +250,7 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
         arena._post(counters, cap)
     s.cfg, s.keep, s.geom, s.img, s.binning, s.cap, s.radii, s.counters = cfg, keep, geom, img, binning, cap, radii, counters
     s.N, s.H, s.W, s.M = N, H, W, M
+    s.arena, s.frame_no = arena, (arena.frames if arena is not None else 0)
     return color, radii, depth, alpha, s
 
 
@@ -334,6 +342,44 @@ def rasterize_backward(s: _Saved, means3D, shs, colors_precomp, opacities, scale
     return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, g_dscaling
 
 
+def _recolor_state(s: _Saved):
+    """A saved state whose lists are still the ones its frame composited."""
+    arena = getattr(s, "arena", None)
+    if arena is not None and arena.frames != s.frame_no:
+        raise L.RiggsHipError("this frame's arena has rendered %d frame(s) since: its binning buffer holds their tile lists, not this "
+                              "frame's — recolour a frame before the next one goes through the same RasterArena"
+                              % (arena.frames - s.frame_no))
+    return s
+
+
+def recolor_forward(s: _Saved, colors, bg):
+    """Composites another colour set over the tile lists of the frame ``s`` (the saved state ``rasterize_forward`` returns):
+    ``(3, H, W)`` = sum_i colors[i] alpha_i T_i + final_T * bg over the very instances the frame composited
+    (riggs_raster_recolor_forward: no preprocess, no sort, no binning; the frame's arenas are only read).  ``colors``: (N, 3),
+    ``bg``: (3,), this call's own.  One launch on the current stream; an overflowed frame gives a zero image (device-side guard)."""
+    _recolor_state(s)
+    colors = L.require_cuda_f32("colors", colors, (s.N, 3))
+    dev = s.img.device
+    bg = L.require_cuda_f32("bg", (bg if bg.device == dev else bg.to(dev)).reshape(-1), (3,))
+    out = torch.empty(3, s.H, s.W, dtype=torch.float32, device=dev)
+    L.check(L.lib().riggs_raster_recolor_forward(C.byref(s.cfg), s.geom.data_ptr(), s.binning.data_ptr(), s.cap, s.img.data_ptr(),
+                                                 s.counters.data_ptr(), L.ptr(colors), bg.data_ptr(), out.data_ptr(), L.stream_ptr()),
+            "riggs_raster_recolor_forward")
+    return out
+
+
+def recolor_backward(s: _Saved, grad_color):
+    """dL/dcolors (N, 3) of ``recolor_forward`` for the image cotangent ``grad_color`` (3, H, W): the colour gradient only
+    (riggs_raster_recolor_backward).  The buffer is zero-filled by the call itself; an overflowed frame gives zeros."""
+    _recolor_state(s)
+    gc = L.require_cuda_f32("grad_color", grad_color, (3, s.H, s.W))
+    g = torch.empty(s.N, 3, dtype=torch.float32, device=s.img.device)
+    L.check(L.lib().riggs_raster_recolor_backward(C.byref(s.cfg), s.geom.data_ptr(), s.binning.data_ptr(), s.cap, s.img.data_ptr(),
+                                                  s.counters.data_ptr(), gc.data_ptr(), L.ptr(g), L.stream_ptr()),
+            "riggs_raster_recolor_backward")
+    return g
+
+
 _WORKSPACES = {}
 _LAST_WORKSPACE = [None, 0]
 _MEANS2D = {}              # (device, stream, N) -> persistent screen-space gradient buffer of the sparse mode
@@ -373,10 +419,13 @@ def _backward_workspace(nbytes: int, dev, N: int) -> torch.Tensor:
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, arena=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, arena=None,
+                keep=None):
         ctx.set_materialize_grads(False)
         color, radii, depth, alpha, s = rasterize_forward(settings, means3D, sh, colors_precomp, opacities, scales,
                                                           rotations, cov3Ds_precomp, arena=arena)
+        if keep is not None:  # (a list: the caller wants the frame's saved state — ``render(keep_lists=True)``)
+            keep.append(s)
         ctx.s, ctx.arena = s, arena
         ctx.save_for_backward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.mark_non_differentiable(radii)
@@ -390,7 +439,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         g = rasterize_backward(ctx.s, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, None,
                                None, grad_color, grad_depth, grad_alpha)
         g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, _ = g
-        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, None, None
+        return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov, None, None, None
 
 
 def _prep(name, t, shape):
@@ -400,12 +449,14 @@ def _prep(name, t, shape):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, arena: Optional[RasterArena] = None):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, arena: Optional[RasterArena] = None, keep: Optional[list] = None):
         """``arena`` (an addition to upstream's signature): a persistent ``RasterArena``; from its second frame on the instance
-        count stays on the device (no host read per call), which a captured iteration needs."""
+        count stays on the device (no host read per call), which a captured iteration needs.  ``keep`` (an addition): a list
+        that every forward appends its frame's saved state to (what ``recolor_forward`` composites over)."""
         super().__init__()
         self.raster_settings = raster_settings
         self.arena = arena
+        self.keep = keep
 
     def markVisible(self, positions):
         """Frustum test of upstream's markVisible: view-space z > 0.2."""
@@ -432,7 +483,7 @@ class GaussianRasterizer(nn.Module):
         rotations = L.require_cuda_f32("rotations", rotations, (N, 4)) if rotations is not None else None
         cov3D_precomp = L.require_cuda_f32("cov3D_precomp", cov3D_precomp, (N, 6)) if cov3D_precomp is not None else None
         return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                         cov3D_precomp, self.raster_settings, self.arena)
+                                         cov3D_precomp, self.raster_settings, self.arena, self.keep)
 
 
 # ---- debugging / test access to the opaque arenas --------------------------------------

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib as L
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, RasterArena, rasterize_forward,
-                         rasterize_backward, arena_check)
+                         rasterize_backward, arena_check, recolor_forward, recolor_backward)
 
 
 def quaternion_multiply(a, b):
@@ -32,6 +32,8 @@ class RenderPkg(dict):
     """The dict ``render`` returns.  ``visibility_filter`` (= ``radii > 0``, gaussian_renderer/__init__.py:147) is
     an elementwise launch that training does not need every frame: it is evaluated on first access.  With
     ``cache=False`` (static buffers of a replayed hipGraph) it is re-evaluated on every access."""
+
+    lists = None  # render(keep_lists=True): the frame's saved state, what ``render(lists=...)`` / ``recolor`` composite over
 
     def __init__(self, *a, cache=True, **k):
         super().__init__(*a, **k)
@@ -78,7 +80,7 @@ class _FusedGlueRaster(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, f_dc, f_rest, opacity, scaling, rotation, d_xyz, d_rot, d_scaling, settings,
-                isotropic, arena):
+                isotropic, arena, keep=None):
         ctx.set_materialize_grads(False)
         N = xyz.shape[0]
         f_dc = L.require_cuda_f32("_features_dc", f_dc, (N, 1, 3))      # read in place: no torch.cat, the kernel
@@ -94,6 +96,8 @@ class _FusedGlueRaster(torch.autograd.Function):
                                 d_rotation=d_rot, d_scaling=d_scaling, glue=True, isotropic=isotropic, arena=arena,
                                 shs_rest=f_rest)
         color, radii, depth, alpha, s = out
+        if keep is not None:  # (render(keep_lists=True): the caller wants the frame's saved state)
+            keep.append(s)
         ctx.s, ctx.arena, ctx.settings, ctx.isotropic = s, arena, settings, isotropic
         ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, d_xyz, d_rot, d_scaling)
         ctx.mark_non_differentiable(radii)
@@ -115,7 +119,7 @@ class _FusedGlueRaster(torch.autograd.Function):
         # instead of cloning them because they are referenced twice
         return (g_means3D, g_means2D, g_dc, g_rest, g_opac, g_scales, g_rots,
                 g_means3D.detach() if d_xyz is not None else None, g_rots.detach() if d_rot is not None else None,
-                g_ds, None, None, None)
+                g_ds, None, None, None, None)
 
 
 def _extension_frame(settings, pc, arena, dx, dr, ds, scaling, iso, screenspace_points):
@@ -153,12 +157,93 @@ def _is_zero_scalar(v):
     return (not isinstance(v, torch.Tensor)) and float(v) == 0.0
 
 
+class _Recolor(torch.autograd.Function):
+    """A second colour set composited over a rendered frame's tile lists as ONE autograd node (csrc/recolor.hip): a launch
+    forward, a memset and a launch backward; differentiable w.r.t. the colours only."""
+
+    @staticmethod
+    def forward(ctx, colors, bg, lists):
+        ctx.lists = lists
+        return recolor_forward(lists, colors, bg)
+
+    @staticmethod
+    def backward(ctx, g_image):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return recolor_backward(ctx.lists, g_image), None, None
+
+
+def recolor(lists, colors, bg):
+    """The ``(3, H, W)`` image of the frame ``lists`` belongs to — ``render(..., keep_lists=True).lists``, or the saved state of
+    ``rasterize_forward`` — with the per-Gaussian colours ``colors`` (N, 3) over the background ``bg`` (3,): the same camera,
+    the same geometry, the same contributors per pixel, nothing projected or sorted again.  Differentiable w.r.t. ``colors``
+    only (the geometry is the main frame's: it gets its gradient from the main frame's image).  ``lists`` must be recoloured
+    before another frame is rendered through its ``RasterArena`` (``RiggsHipError`` otherwise)."""
+    return _Recolor.apply(colors, bg, lists)
+
+
+def _render_over_lists(lists, viewpoint_camera, pc, pipe, bg, xyz, d_color, override_color, render_motion, scale_const):
+    """``render(lists=...)``: the checks that need no device work first, then the colours of the general path composited by
+    ``recolor``.  ``lists``: the saved state of the main render (``N``, ``H``, ``W`` and, after the checks, its arenas)."""
+    if not render_motion and override_color is None:
+        raise ValueError("render(lists=...) recolours the main frame: it needs render_motion=True or override_color=...")
+    if scale_const is not None:
+        raise ValueError("render(lists=...) cannot take scale_const: the lists were built from the main frame's scales and opacities")
+    N, H, W = int(xyz.shape[0]), int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    if int(lists.N) != N:
+        raise ValueError("render(lists=...): the lists belong to %d Gaussians, the model has %d" % (int(lists.N), N))
+    if (int(lists.H), int(lists.W)) != (H, W):
+        raise ValueError("render(lists=...): the lists belong to a %d x %d image, the camera renders %d x %d"
+                         % (int(lists.H), int(lists.W), H, W))
+    if pipe.debug:  # (two small device comparisons and a host read each: with pipe.debug only)
+        view, proj = getattr(lists, "view", None), getattr(lists, "proj", None)
+        if view is None or not torch.equal(view, viewpoint_camera.world_view_transform) \
+                or not torch.equal(proj, viewpoint_camera.full_proj_transform):
+            raise ValueError("render(lists=...): the camera is not the main render's (view / projection matrices differ)")
+    colour = _general_colour(pc, pipe, viewpoint_camera, xyz, d_color, override_color, render_motion)["colors_precomp"]
+    image = recolor(lists, colour, bg)
+    main = lists.outputs  # (radii, depth, alpha) of the main frame
+    return RenderPkg({"render": image, "viewspace_points": torch.zeros(N, 3, dtype=torch.float32, device=xyz.device),
+                      "visibility_filter": None, "radii": main[0], "depth": main[1], "alpha": main[2], "bg_color": bg})
+
+
+def _kept(pkg, keep, viewpoint_camera, radii, depth, alpha):
+    """``render(keep_lists=True)``: the frame's saved state, with what ``render(lists=...)`` hands on, as ``pkg.lists``."""
+    s = keep[0]
+    s.view, s.proj = viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform
+    s.outputs = (radii, depth.detach(), alpha.detach())
+    pkg.lists = s
+    return pkg
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, d_xyz, d_rotation, d_scaling, d_opacity=None, d_color=None,
            scaling_modifier=1.0, override_color=None, random_bg_color=False, render_motion=False, detach_xyz=False,
            detach_scale=False, detach_rot=False, detach_opacity=False, d_rot_as_res=True, scale_const=None,
-           d_rotation_bias=None, force_visible=False, fused=True, arena: RasterArena = None):
-    """Same contract as the reference ``render`` (returns the same dict).  ``fused`` / ``arena`` are additions."""
+           d_rotation_bias=None, force_visible=False, fused=True, arena: RasterArena = None, keep_lists=False, lists=None):
+    """Same contract as the reference ``render`` (returns the same dict).  ``fused`` / ``arena`` / ``keep_lists`` / ``lists``
+    are additions; with neither of the last two every code path is what it was without them.
+
+    ``keep_lists=True``: the returned ``RenderPkg`` carries the frame's saved state — tile lists, conics, transmittances,
+    contributor counts — as the ATTRIBUTE ``.lists`` (not a key: the dict keeps the reference's seven).  The frame then goes
+    through the ctypes autograd node, not the PyTorch extension's C++ node, which keeps its state to itself: a host-bound eager
+    trainer pays that node's host time on this frame.
+
+    ``lists=main.lists``: a second render of the SAME camera and geometry that differs only in the colour — legal with
+    ``render_motion=True`` or ``override_color=...`` only (``ValueError`` otherwise, and for ``scale_const``, another N or
+    another image size).  The caller promises that the camera and every geometry argument are the main render's; with
+    ``pipe.debug`` the view and projection matrices are compared and a mismatch raises.  The colours are formed as the general
+    path forms them and composited over the main frame's lists by ``recolor`` (csrc/recolor.hip) over ``bg_color`` (or a fresh
+    ``rand_like`` under ``random_bg_color``): no preprocess, no sort, no binning, and a backward that computes dL/dcolour and
+    nothing else.  ``radii``, ``depth``, ``alpha`` and ``visibility_filter`` of the returned dict are the main frame's tensors.
+    Deviation from the reference, on purpose: ``viewspace_points`` is a zero (N, 3) tensor that receives no gradient — the
+    reference would fill this second render's own screen-space gradient, which no caller reads (train_gui.py:1060 takes the
+    first render's).  ``lists`` must be used before another frame goes through the main render's arena."""
     xyz = pc.get_xyz
+    if lists is not None:
+        if keep_lists:
+            raise ValueError("render(lists=...) renders no frame of its own: keep_lists=True belongs on the main render")
+        bg = bg_color if not random_bg_color else torch.rand_like(bg_color)
+        return _render_over_lists(lists, viewpoint_camera, pc, pipe, bg, xyz, d_color, override_color, render_motion, scale_const)
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
     bg = bg_color if not random_bg_color else torch.rand_like(bg_color)
@@ -179,15 +264,17 @@ def render(viewpoint_camera, pc, pipe, bg_color, d_xyz, d_rotation, d_scaling, d
         ds = None if _is_zero_scalar(d_scaling) else d_scaling
         iso = bool(getattr(pc, "use_isotropic_gs", False))
         scaling = pc._scaling[..., :1] if iso else pc._scaling
-        fast = _extension_frame(settings, pc, arena, dx, dr, ds, scaling, iso, screenspace_points)
+        keep = [] if keep_lists else None
+        fast = None if keep_lists else _extension_frame(settings, pc, arena, dx, dr, ds, scaling, iso, screenspace_points)
         if fast is not None:
             color, radii, depth, alpha = fast
         else:
             color, radii, depth, alpha = _FusedGlueRaster.apply(
                 pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, scaling, pc._rotation,
-                dx, dr, ds, settings, iso, arena)
-        return RenderPkg({"render": color, "viewspace_points": screenspace_points, "visibility_filter": None,
-                          "radii": radii, "depth": depth, "alpha": alpha, "bg_color": bg})
+                dx, dr, ds, settings, iso, arena, keep)
+        pkg = RenderPkg({"render": color, "viewspace_points": screenspace_points, "visibility_filter": None,
+                         "radii": radii, "depth": depth, "alpha": alpha, "bg_color": bg})
+        return _kept(pkg, keep, viewpoint_camera, radii, depth, alpha) if keep_lists else pkg
 
     # ---- general path: every optional branch of the reference's render(), resolved by three small helpers and
     # handed to the drop-in GaussianRasterizer (the activations are torch ops here; the rasterizer is HIP)
@@ -200,10 +287,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, d_xyz, d_rotation, d_scaling, d
     shape = {k: cut(v, (detach_rot or detach_scale) if k == "cov3D_precomp" else
                     (detach_rot if k == "rotations" else detach_scale)) for k, v in shape.items()}
     colour = _general_colour(pc, pipe, viewpoint_camera, xyz, d_color, override_color, render_motion)
-    image, radii, depth, alpha = GaussianRasterizer(raster_settings=settings)(
+    keep = [] if keep_lists else None
+    image, radii, depth, alpha = GaussianRasterizer(raster_settings=settings, keep=keep)(
         means3D=means3D, means2D=screenspace_points, opacities=cut(opacity, detach_opacity), **shape, **colour)
-    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-            "depth": depth, "alpha": alpha, "bg_color": bg}
+    out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+           "depth": depth, "alpha": alpha, "bg_color": bg}
+    return _kept(RenderPkg(out), keep, viewpoint_camera, radii, depth, alpha) if keep_lists else out
 
 
 class _FlowColors(torch.autograd.Function):
