@@ -119,6 +119,10 @@ struct BinLayout {
 #define RIGGS_CKPT_FLOATS (5 * 256)  // floats per checkpoint slot
 BinLayout bin_layout(int64_t cap, int N, int H, int W);
 
+// ---- exp on the hardware's exp2 (compositing alpha, skinning weights) ------
+#define LOG2E 1.4426950408889634f
+__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
+
 // ---- wave64 reductions -----------------------------------------------------
 // Sum over the 64 lanes of a wave using DPP row operations + two cross-row steps.
 __device__ __forceinline__ float wave_sum(float v) {

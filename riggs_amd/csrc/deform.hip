@@ -9,9 +9,6 @@
 
 namespace riggs {
 
-#define LOG2E 1.4426950408889634f
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
-
 __global__ __launch_bounds__(64) void fk_forward_kernel(int J, const float* __restrict__ local_rot,
                                                         const float* __restrict__ joints,
                                                         const int32_t* __restrict__ parents,

@@ -4,6 +4,10 @@
 
 namespace riggs {
 
+// alpha of a compositing step: contributions below ALPHA_MIN are skipped, alpha is clamped to ALPHA_MAX (render.hip, recolor.hip)
+#define ALPHA_MIN (1.0f / 255.0f)
+#define ALPHA_MAX 0.99f
+
 // SH colour evaluation as a job of Gaussian blocks (color_job.h) that the tile sort's scatter launch hosts.  The record lives
 // in the geometry arena: preprocess_fwd writes it (N = 0: it evaluated the colours itself), the hosting launch reads it.
 struct ColorJob {

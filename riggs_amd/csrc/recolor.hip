@@ -14,12 +14,8 @@
 
 namespace riggs {
 
-// the alpha evaluation of render_bwd_kernel (render.hip) on the geometry arena: same constants, same expression order, same tests
-#define ALPHA_MIN (1.0f / 255.0f)
-#define ALPHA_MAX 0.99f
-#define LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
+// the alpha evaluation of render_bwd_kernel (render.hip) on the geometry arena: the same constants (raster_internal.h), the same
+// expression order, the same tests
 
 struct RecolorArgs {
   int W, H, N;

@@ -12,12 +12,7 @@
 
 namespace riggs {
 
-#define ALPHA_MIN (1.0f / 255.0f)
-#define ALPHA_MAX 0.99f
 #define T_EPS 0.0001f
-#define LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
 
 #define QP(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 #define QUAD_F(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (float)(v)), ctrl, 0xf, 0xf, true))

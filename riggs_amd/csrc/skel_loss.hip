@@ -1,58 +1,73 @@
-// Skeleton projection loss of the trainer (second half):
-//   TrainRig.cal_skeleton_loss        /root/reference/train_rig.py:309-314   (weight 1e-3 by default, arguments/__init__.py:184)
-//   TrainRig.sampling_skeleton_points /root/reference/train_rig.py:264-276
+// Projection losses of the trainers: a point set of the POSED skeleton is projected with the camera's pinhole and compared with
+// the M thinned-silhouette pixels of the frame by a two-sided L1 chamfer distance (mean of nearest-neighbour distances in either
+// direction).  ONE implementation over two point sets (a compile-time policy, `template <bool BONES>`):
+//   bone form (second half): S equally spaced points on each of the J-1 bones, P = S (J-1)
+//     TrainRig.cal_skeleton_loss        /root/reference/train_rig.py:309-314   (weight 1e-3 by default, arguments/__init__.py:184)
+//     TrainRig.sampling_skeleton_points /root/reference/train_rig.py:264-276
+//   node form (stage 1, /root/reference/train_gui.py:1133-1139): the J control nodes themselves, P = J (parents, t unused; S = 1)
 //   project_nodes_to_2d_elements      /root/reference/utils/other_utils.py:101-127
 //   pytorch3d.loss.chamfer_distance(x, y, norm=1)   — third-party, not vendored: restated from its published definition
-// S equally spaced points on each of the J-1 bones of the POSED skeleton are projected with the camera's pinhole and
-// compared with the M thinned-silhouette pixels of the frame by a two-sided L1 chamfer distance (mean of nearest-neighbour
-// distances in either direction).  The reference builds ~20 small tensors and a KNN extension call and lets autograd replay
-// them; here the forward is a memset and two launches (all-pairs nearest neighbours of both directions in one grid; a
-// fixed-order reduction) and the backward two (per-bone gradient incl. the pull of the pixels on their points, per-joint
-// gather), all deterministic: the only atomics are 64-bit max and integer adds.  Sizes are tiny (P = S (J-1) ≈ 0.5-3 k
-// points, M ≈ 0.1-5 k pixels): the work is launch-bound, so it is kept to four kernel nodes of a captured iteration.
+// Only how point p is formed from `nodes`, and how its gradient reaches the joints, differs between the forms.  The reference
+// builds ~20 small tensors and a KNN extension call and lets autograd replay them; here the forward is a memset and two launches
+// (all-pairs nearest neighbours of both directions in one grid; a fixed-order reduction) and the backward two for the bones
+// (per-bone gradient incl. the pull of the pixels on their points, per-joint gather), one for the nodes, all deterministic: the
+// only atomics are 64-bit max and integer adds.  Sizes are tiny (P ≈ 0.5-3 k points, M ≈ 0.1-5 k pixels): the work is
+// launch-bound, so the bone form is kept to four kernel nodes of a captured iteration.
 #include "common.h"
 
 namespace riggs {
 
 struct SkelProjArgs {
   int J, S, M, P;
-  const int* parents;
+  const int* parents;   // (bone form)
   const float* nodes;   // (J, 3) posed joints
-  const float* t;       // (S) line parameters
+  const float* t;       // (S) line parameters (bone form)
   const float* view;    // (4, 4) world_view_transform as the reference stores it (row-vector convention)
   float fx, fy, cx, cy;
   const float* thinned; // (M, 2) (row, col)
   const int* m_dev;     // optional device-side pixel count (<= M = the buffer's capacity): one captured graph, any frame
   // state, zeroed by one memset node at the head of the forward:
   unsigned long long* near_x;  // (P) ~(distance bits << 32 | index of the nearest pixel): atomicMax = nearest, lowest index
-  unsigned long long* near_y;  // (M) the same for every pixel over the sample points
-  float* bone_grad;            // (J-1, 6) child part, parent part
+  unsigned long long* near_y;  // (M) the same for every pixel over the points
+  float* bone_grad;            // (J-1, 6) child part, parent part (bone form)
 };
 
 __device__ __forceinline__ int skel_pixels(const SkelProjArgs& a) { return a.m_dev ? min(max(a.m_dev[0], 1), a.M) : a.M; }
 
-// point p = s (J-1) + (k-1) lies on bone k (child k, parent parents[k]) at parameter t[s]
-__device__ __forceinline__ void skel_point(const SkelProjArgs& a, int p, float& tx, float& ty, float& tz, float& tt, int& k) {
-  const int nb = a.J - 1;
-  const int s = p / nb;
-  k = p - s * nb + 1;
-  const int par = a.parents[k];
-  tt = a.t[s];
-  const float u = 1.0f - tt;
-  const float px = tt * a.nodes[3 * k + 0] + u * a.nodes[3 * par + 0];
-  const float py = tt * a.nodes[3 * k + 1] + u * a.nodes[3 * par + 1];
-  const float pz = tt * a.nodes[3 * k + 2] + u * a.nodes[3 * par + 2];
+// Point p in camera space.  BONES: p = s (J-1) + (k-1) lies on bone k (child k, parent parents[k]) at parameter tt = t[s];
+// otherwise p is node p (tt is not set).
+template <bool BONES>
+__device__ __forceinline__ void skel_point(const SkelProjArgs& a, int p, float& tx, float& ty, float& tz, float& tt) {
+  float px, py, pz;
+  if constexpr (BONES) {
+    const int nb = a.J - 1;
+    const int s = p / nb;
+    const int k = p - s * nb + 1;
+    const int par = a.parents[k];
+    tt = a.t[s];
+    const float u = 1.0f - tt;
+    px = tt * a.nodes[3 * k + 0] + u * a.nodes[3 * par + 0];
+    py = tt * a.nodes[3 * k + 1] + u * a.nodes[3 * par + 1];
+    pz = tt * a.nodes[3 * k + 2] + u * a.nodes[3 * par + 2];
+  } else {
+    px = a.nodes[3 * p + 0]; py = a.nodes[3 * p + 1]; pz = a.nodes[3 * p + 2];
+  }
   const float* V = a.view;
   tx = px * V[0] + py * V[4] + pz * V[8] + V[12];
   ty = px * V[1] + py * V[5] + pz * V[9] + V[13];
   tz = px * V[2] + py * V[6] + pz * V[10] + V[14];
 }
 
+// the pinhole: (row, col) of a camera-space point
+__device__ __forceinline__ float2 skel_pinhole(const SkelProjArgs& a, float tx, float ty, float tz) {
+  return make_float2(a.fy * ty / tz + a.cy, a.fx * tx / tz + a.cx);
+}
+
+template <bool BONES>
 __device__ __forceinline__ float2 skel_project(const SkelProjArgs& a, int p) {
   float tx, ty, tz, tt;
-  int k;
-  skel_point(a, p, tx, ty, tz, tt, k);
-  return make_float2(a.fy * ty / tz + a.cy, a.fx * tx / tz + a.cx);
+  skel_point<BONES>(a, p, tx, ty, tz, tt);
+  return skel_pinhole(a, tx, ty, tz);
 }
 
 // All-pairs nearest neighbours, both directions in one grid of single-wave workgroups: a workgroup takes 64 queries and a
@@ -61,9 +76,10 @@ __device__ __forceinline__ float2 skel_project(const SkelProjArgs& a, int p) {
 // Projections are recomputed wherever they are needed (40 flops) instead of a separate launch and a round trip through HBM.
 #define SKEL_Q 64
 #define SKEL_C 256
+template <bool BONES>
 __global__ void __launch_bounds__(SKEL_Q) skel_nearest_kernel(SkelProjArgs a, int n_xblocks, int n_yslices_of_x) {
   __shared__ float2 s_c[SKEL_C];
-  const bool xdir = (int)blockIdx.x < n_xblocks;  // queries = sample points, candidates = pixels
+  const bool xdir = (int)blockIdx.x < n_xblocks;  // queries = points, candidates = pixels
   int qb, cs;
   if (xdir) { qb = blockIdx.x / n_yslices_of_x; cs = blockIdx.x - qb * n_yslices_of_x; }
   else {
@@ -76,9 +92,9 @@ __global__ void __launch_bounds__(SKEL_Q) skel_nearest_kernel(SkelProjArgs a, in
   const int base = cs * SKEL_C, n = min(SKEL_C, nc - base);
   if (n <= 0 || qb * SKEL_Q >= nq) return;  // beyond the frame's pixel count (the grid is sized for the capacity)
   const float2* pix = reinterpret_cast<const float2*>(a.thinned);
-  for (int j = threadIdx.x; j < n; j += SKEL_Q) s_c[j] = xdir ? pix[base + j] : skel_project(a, base + j);
+  for (int j = threadIdx.x; j < n; j += SKEL_Q) s_c[j] = xdir ? pix[base + j] : skel_project<BONES>(a, base + j);
   float2 me = make_float2(0.f, 0.f);
-  if (i < nq) me = xdir ? skel_project(a, i) : pix[i];
+  if (i < nq) me = xdir ? skel_project<BONES>(a, i) : pix[i];
   __syncthreads();
   float best = 3.0e38f;
   int bj = 0;
@@ -120,9 +136,31 @@ __global__ void __launch_bounds__(1024) skel_finish_kernel(SkelProjArgs a, const
   }
 }
 
-// One workgroup per bone.  (i) every pixel that chose a sample point of this bone adds its pull sign(proj - pixel) to the
+// upstream gradient of the loss (g_loss on loss, g_weighted on weight * loss) per point (wx) and per pixel (wy)
+__device__ __forceinline__ void skel_grad_scale(const SkelProjArgs& a, int M, const float* g_loss, const float* g_weighted,
+                                                const float* weight, float& wx, float& wy) {
+  const float g = (g_loss ? g_loss[0] : 0.f) + (g_weighted ? g_weighted[0] * (weight ? weight[0] : 1.f) : 0.f);
+  wx = g / (float)a.P;
+  wy = g / (float)M;
+}
+
+// dL/d(world point) of the point at (tx, ty, tz) in camera space: its own nearest pixel `ix` plus the pulls of the pixels that
+// chose it, w.r.t. its projection, back through the pinhole and the view transform.
+__device__ __forceinline__ float3 skel_point_grad(const SkelProjArgs& a, float tx, float ty, float tz, int ix, int pull_y, int pull_x,
+                                                  float wx, float wy) {
+  const float2 pr = skel_pinhole(a, tx, ty, tz);
+  const float gy = wx * sgn(pr.x - a.thinned[2 * ix + 0]) + wy * (float)pull_y;
+  const float gx = wx * sgn(pr.y - a.thinned[2 * ix + 1]) + wy * (float)pull_x;
+  const float iz = 1.0f / tz;
+  const float gtx = gx * a.fx * iz, gty = gy * a.fy * iz;
+  const float gtz = -(gy * a.fy * ty + gx * a.fx * tx) * iz * iz;
+  const float* V = a.view;
+  return make_float3(gtx * V[0] + gty * V[1] + gtz * V[2], gtx * V[4] + gty * V[5] + gtz * V[6], gtx * V[8] + gty * V[9] + gtz * V[10]);
+}
+
+// Bone form: one workgroup per bone.  (i) every pixel that chose a sample point of this bone adds its pull sign(proj - pixel) to the
 // point — integer counters in LDS, exact under any order; (ii) gradient of every sample point w.r.t. its projection (its own
-// nearest pixel plus the pulls), back through the pinhole and the view transform, split between the bone's two joints;
+// nearest pixel plus the pulls: skel_point_grad), split between the bone's two joints;
 // (iii) fixed-order reduction over the workgroup.
 #define SKEL_MAX_S 2048
 __global__ void __launch_bounds__(256) skel_bone_grad_kernel(SkelProjArgs a, const float* g_loss, const float* g_weighted,
@@ -139,34 +177,23 @@ __global__ void __launch_bounds__(256) skel_bone_grad_kernel(SkelProjArgs a, con
     const int p = (int)(unsigned)(~a.near_y[m]);
     const int s = p / nb;
     if (p - s * nb != kb) continue;
-    const float2 pr = skel_project(a, p);
+    const float2 pr = skel_project<true>(a, p);
     const int sy = (int)sgn(pr.x - a.thinned[2 * m + 0]), sx = (int)sgn(pr.y - a.thinned[2 * m + 1]);
     if (sy) atomicAdd(&s_pull[s][0], sy);
     if (sx) atomicAdd(&s_pull[s][1], sx);
   }
   __syncthreads();
-  const float g = (g_loss ? g_loss[0] : 0.f) + (g_weighted ? g_weighted[0] * (weight ? weight[0] : 1.f) : 0.f);
-  const float wx = g / (float)a.P, wy = g / (float)M;
+  float wx, wy;
+  skel_grad_scale(a, M, g_loss, g_weighted, weight, wx, wy);
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int s = threadIdx.x; s < a.S; s += 256) {
     const int p = s * nb + kb;
     float tx, ty, tz, tt;
-    int k;
-    skel_point(a, p, tx, ty, tz, tt, k);
-    const float py = a.fy * ty / tz + a.cy, px = a.fx * tx / tz + a.cx;
-    const int ix = (int)(unsigned)(~a.near_x[p]);
-    const float gy = wx * sgn(py - a.thinned[2 * ix + 0]) + wy * (float)s_pull[s][0];
-    const float gx = wx * sgn(px - a.thinned[2 * ix + 1]) + wy * (float)s_pull[s][1];
-    const float iz = 1.0f / tz;
-    const float gtx = gx * a.fx * iz, gty = gy * a.fy * iz;
-    const float gtz = -(gy * a.fy * ty + gx * a.fx * tx) * iz * iz;
-    const float* V = a.view;
-    const float g0 = gtx * V[0] + gty * V[1] + gtz * V[2];
-    const float g1 = gtx * V[4] + gty * V[5] + gtz * V[6];
-    const float g2 = gtx * V[8] + gty * V[9] + gtz * V[10];
+    skel_point<true>(a, p, tx, ty, tz, tt);
+    const float3 g = skel_point_grad(a, tx, ty, tz, (int)(unsigned)(~a.near_x[p]), s_pull[s][0], s_pull[s][1], wx, wy);
     const float u = 1.0f - tt;
-    acc[0] += tt * g0; acc[1] += tt * g1; acc[2] += tt * g2;
-    acc[3] += u * g0;  acc[4] += u * g1;  acc[5] += u * g2;
+    acc[0] += tt * g.x; acc[1] += tt * g.y; acc[2] += tt * g.z;
+    acc[3] += u * g.x;  acc[4] += u * g.y;  acc[5] += u * g.z;
   }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
@@ -189,80 +216,8 @@ __global__ void skel_joint_gather_kernel(SkelProjArgs a, float* grad_nodes) {
   }
 }
 
-static int skel_fill(SkelProjArgs& a, int J, int S, int M, const int32_t* parents, const float* d_nodes, const float* t,
-                     const float* view, float fx, float fy, float cx, float cy, const float* thinned, const int32_t* pixel_count,
-                     float* state) {
-  RIGGS_REQUIRE(J >= 2 && J <= 4096, "need 2..4096 joints");
-  RIGGS_REQUIRE(S >= 1 && M >= 1, "empty point set: the reference's mean over it is undefined");
-  RIGGS_REQUIRE(S <= SKEL_MAX_S, "more than 2048 samples per bone");
-  RIGGS_REQUIRE((size_t)S * (J - 1) < (1u << 30) && M < (1 << 30), "point set too large");
-  RIGGS_REQUIRE(parents && d_nodes && t && view && thinned && state, "NULL buffer");
-  memset(&a, 0, sizeof(a));
-  a.J = J; a.S = S; a.M = M; a.P = S * (J - 1);
-  a.parents = parents; a.nodes = d_nodes; a.t = t; a.view = view;
-  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.thinned = thinned; a.m_dev = pixel_count;
-  RIGGS_REQUIRE(((uintptr_t)state & 7) == 0, "state must be 8-byte aligned");
-  float* f = state;
-  a.near_x = (unsigned long long*)f;  f += 2 * (size_t)a.P;
-  a.near_y = (unsigned long long*)f;  f += 2 * (size_t)M;
-  a.bone_grad = f;
-  return 0;
-}
-
-
-// ---- node projection term of stage 1 (/root/reference/train_gui.py:1133-1139) -------------------------------------------------
-// The point set is the J control nodes themselves: no bones, no sampling steps (P = J).  Kernels and entry points of its own —
-// everything above is the bone form, untouched — that share the argument block (parents, t unused; S = 1), the key format,
-// `skel_pixels` and `skel_finish_kernel` (which only sees P, M and the keys).
-__device__ __forceinline__ void node_point(const SkelProjArgs& a, int p, float& tx, float& ty, float& tz) {
-  const float px = a.nodes[3 * p + 0], py = a.nodes[3 * p + 1], pz = a.nodes[3 * p + 2];
-  const float* V = a.view;
-  tx = px * V[0] + py * V[4] + pz * V[8] + V[12];
-  ty = px * V[1] + py * V[5] + pz * V[9] + V[13];
-  tz = px * V[2] + py * V[6] + pz * V[10] + V[14];
-}
-__device__ __forceinline__ float2 node_project(const SkelProjArgs& a, int p) {
-  float tx, ty, tz;
-  node_point(a, p, tx, ty, tz);
-  return make_float2(a.fy * ty / tz + a.cy, a.fx * tx / tz + a.cx);
-}
-
-// all-pairs nearest neighbours, both directions in one grid: the shape of skel_nearest_kernel over the nodes' projections
-__global__ void __launch_bounds__(SKEL_Q) node_nearest_kernel(SkelProjArgs a, int n_xblocks, int n_yslices_of_x) {
-  __shared__ float2 s_c[SKEL_C];
-  const bool xdir = (int)blockIdx.x < n_xblocks;  // queries = nodes, candidates = pixels
-  int qb, cs;
-  if (xdir) { qb = blockIdx.x / n_yslices_of_x; cs = blockIdx.x - qb * n_yslices_of_x; }
-  else {
-    const int r = blockIdx.x - n_xblocks, n_slices = (a.P + SKEL_C - 1) / SKEL_C;
-    qb = r / n_slices; cs = r - qb * n_slices;
-  }
-  const int M = skel_pixels(a);
-  const int nq = xdir ? a.P : M, nc = xdir ? M : a.P;
-  const int i = qb * SKEL_Q + threadIdx.x;
-  const int base = cs * SKEL_C, n = min(SKEL_C, nc - base);
-  if (n <= 0 || qb * SKEL_Q >= nq) return;  // beyond the frame's pixel count (the grid is sized for the capacity)
-  const float2* pix = reinterpret_cast<const float2*>(a.thinned);
-  for (int j = threadIdx.x; j < n; j += SKEL_Q) s_c[j] = xdir ? pix[base + j] : node_project(a, base + j);
-  float2 me = make_float2(0.f, 0.f);
-  if (i < nq) me = xdir ? node_project(a, i) : pix[i];
-  __syncthreads();
-  float best = 3.0e38f;
-  int bj = 0;
-#pragma unroll 8
-  for (int j = 0; j < n; ++j) {
-    const float2 o = s_c[j];
-    const float d = fabsf(me.x - o.x) + fabsf(me.y - o.y);
-    if (d < best) { best = d; bj = j; }
-  }
-  if (i < nq) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)(base + bj);
-    atomicMax((xdir ? a.near_x : a.near_y) + i, ~key);
-  }
-}
-
-// One workgroup per node: the pulls of the pixels that chose it (integer counters in LDS: exact under any order), then its own
-// nearest pixel, back through the pinhole and the view transform.  Deterministic.
+// Node form: one workgroup per node: the pulls of the pixels that chose it (integer counters in LDS: exact under any order), then
+// its own nearest pixel (skel_point_grad).  Deterministic.
 __global__ void __launch_bounds__(256) node_grad_kernel(SkelProjArgs a, const float* g_loss, const float* g_weighted, const float* weight,
                                                         float* grad_nodes) {
   __shared__ int s_pull[2];
@@ -270,45 +225,71 @@ __global__ void __launch_bounds__(256) node_grad_kernel(SkelProjArgs a, const fl
   if (threadIdx.x < 2) s_pull[threadIdx.x] = 0;
   __syncthreads();
   const int M = skel_pixels(a);
-  float tx, ty, tz;
-  node_point(a, j, tx, ty, tz);
-  const float py = a.fy * ty / tz + a.cy, px = a.fx * tx / tz + a.cx;
+  float tx, ty, tz, tt;
+  skel_point<false>(a, j, tx, ty, tz, tt);
+  const float2 pr = skel_pinhole(a, tx, ty, tz);
   int cy_ = 0, cx_ = 0;
   for (int m = threadIdx.x; m < M; m += 256) {
     if ((int)(unsigned)(~a.near_y[m]) != j) continue;
-    cy_ += (int)sgn(py - a.thinned[2 * m + 0]);
-    cx_ += (int)sgn(px - a.thinned[2 * m + 1]);
+    cy_ += (int)sgn(pr.x - a.thinned[2 * m + 0]);
+    cx_ += (int)sgn(pr.y - a.thinned[2 * m + 1]);
   }
   if (cy_) atomicAdd(&s_pull[0], cy_);
   if (cx_) atomicAdd(&s_pull[1], cx_);
   __syncthreads();
   if (threadIdx.x != 0) return;
-  const float g = (g_loss ? g_loss[0] : 0.f) + (g_weighted ? g_weighted[0] * (weight ? weight[0] : 1.f) : 0.f);
-  const float wx = g / (float)a.P, wy = g / (float)M;
-  const int ix = (int)(unsigned)(~a.near_x[j]);
-  const float gy = wx * sgn(py - a.thinned[2 * ix + 0]) + wy * (float)s_pull[0];
-  const float gx = wx * sgn(px - a.thinned[2 * ix + 1]) + wy * (float)s_pull[1];
-  const float iz = 1.0f / tz;
-  const float gtx = gx * a.fx * iz, gty = gy * a.fy * iz;
-  const float gtz = -(gy * a.fy * ty + gx * a.fx * tx) * iz * iz;
-  const float* V = a.view;
-  grad_nodes[3 * j + 0] = gtx * V[0] + gty * V[1] + gtz * V[2];
-  grad_nodes[3 * j + 1] = gtx * V[4] + gty * V[5] + gtz * V[6];
-  grad_nodes[3 * j + 2] = gtx * V[8] + gty * V[9] + gtz * V[10];
+  float wx, wy;
+  skel_grad_scale(a, M, g_loss, g_weighted, weight, wx, wy);
+  const float3 g = skel_point_grad(a, tx, ty, tz, (int)(unsigned)(~a.near_x[j]), s_pull[0], s_pull[1], wx, wy);
+  grad_nodes[3 * j + 0] = g.x; grad_nodes[3 * j + 1] = g.y; grad_nodes[3 * j + 2] = g.z;
 }
 
-static int node_fill(SkelProjArgs& a, int J, int M, const float* d_nodes, const float* view, float fx, float fy, float cx, float cy,
+// The argument block of either form (node form: parents = t = NULL, S = 1, P = J) over the caller's state.
+static int skel_fill(SkelProjArgs& a, int J, int S, int P, int M, const int32_t* parents, const float* d_nodes, const float* t,
+                     const float* view, float fx, float fy, float cx, float cy, const float* thinned, const int32_t* pixel_count,
+                     float* state) {
+  RIGGS_REQUIRE(((uintptr_t)state & 7) == 0, "state must be 8-byte aligned");
+  memset(&a, 0, sizeof(a));
+  a.J = J; a.S = S; a.M = M; a.P = P;
+  a.parents = parents; a.nodes = d_nodes; a.t = t; a.view = view;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.thinned = thinned; a.m_dev = pixel_count;
+  float* f = state;
+  a.near_x = (unsigned long long*)f;  f += 2 * (size_t)P;
+  a.near_y = (unsigned long long*)f;  f += 2 * (size_t)M;
+  if (parents) a.bone_grad = f;
+  return 0;
+}
+
+// The forward of either form: a memset of the two key arrays, the nearest-neighbour grid, the reduction.
+template <bool BONES>
+static int skel_forward(const SkelProjArgs& a, const float* weight, float* loss2, hipStream_t s) {
+  RIGGS_REQUIRE(loss2, "NULL buffer");
+  // zero = "no neighbour yet" for the complemented keys
+  RIGGS_HIP_CHECK(hipMemsetAsync(a.near_x, 0, sizeof(float) * (2 * (size_t)a.P + 2 * (size_t)a.M), s));
+  const int ysl = (a.M + SKEL_C - 1) / SKEL_C, xsl = (a.P + SKEL_C - 1) / SKEL_C;
+  const int n_xblocks = ((a.P + SKEL_Q - 1) / SKEL_Q) * ysl, n_yblocks = ((a.M + SKEL_Q - 1) / SKEL_Q) * xsl;
+  hipLaunchKernelGGL(skel_nearest_kernel<BONES>, dim3(n_xblocks + n_yblocks), dim3(SKEL_Q), 0, s, a, n_xblocks, ysl);
+  hipLaunchKernelGGL(skel_finish_kernel, dim3(1), dim3(1024), 0, s, a, weight, loss2);
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// what the entry points of each form require of their arguments
+static int bone_args(SkelProjArgs& a, int J, int S, int M, const int32_t* parents, const float* d_nodes, const float* t,
+                     const float* view, float fx, float fy, float cx, float cy, const float* thinned, const int32_t* pixel_count,
+                     float* state) {
+  RIGGS_REQUIRE(J >= 2 && J <= 4096, "need 2..4096 joints");
+  RIGGS_REQUIRE(S >= 1 && M >= 1, "empty point set: the reference's mean over it is undefined");
+  RIGGS_REQUIRE(S <= SKEL_MAX_S, "more than 2048 samples per bone");
+  RIGGS_REQUIRE((size_t)S * (J - 1) < (1u << 30) && M < (1 << 30), "point set too large");
+  RIGGS_REQUIRE(parents && d_nodes && t && view && thinned && state, "NULL buffer");
+  return skel_fill(a, J, S, S * (J - 1), M, parents, d_nodes, t, view, fx, fy, cx, cy, thinned, pixel_count, state);
+}
+static int node_args(SkelProjArgs& a, int J, int M, const float* d_nodes, const float* view, float fx, float fy, float cx, float cy,
                      const float* thinned, const int32_t* pixel_count, float* state) {
   RIGGS_REQUIRE(J >= 1 && J < (1 << 30) && M >= 1 && M < (1 << 30), "empty or oversized point set");
   RIGGS_REQUIRE(d_nodes && view && thinned && state, "NULL buffer");
-  RIGGS_REQUIRE(((uintptr_t)state & 7) == 0, "state must be 8-byte aligned");
-  memset(&a, 0, sizeof(a));
-  a.J = J; a.S = 1; a.M = M; a.P = J;
-  a.nodes = d_nodes; a.view = view;
-  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.thinned = thinned; a.m_dev = pixel_count;
-  a.near_x = (unsigned long long*)state;
-  a.near_y = (unsigned long long*)(state + 2 * (size_t)J);
-  return 0;
+  return skel_fill(a, J, 1, J, M, nullptr, d_nodes, nullptr, view, fx, fy, cx, cy, thinned, pixel_count, state);
 }
 
 }  // namespace riggs
@@ -327,17 +308,8 @@ int riggs_skeleton_projection_forward(int32_t J, int32_t S, int32_t M, const int
                                       float cy, const float* thinned, const int32_t* pixel_count, const float* weight, float* state,
                                       float* loss2, riggs_stream stream) {
   SkelProjArgs a;
-  if (int rc = skel_fill(a, J, S, M, parents, d_nodes, t, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
-  RIGGS_REQUIRE(loss2, "NULL buffer");
-  hipStream_t s = (hipStream_t)stream;
-  // zero = "no neighbour yet" for the complemented keys
-  RIGGS_HIP_CHECK(hipMemsetAsync(state, 0, sizeof(float) * (2 * (size_t)a.P + 2 * (size_t)M), s));
-  const int ysl = (M + SKEL_C - 1) / SKEL_C, xsl = (a.P + SKEL_C - 1) / SKEL_C;
-  const int n_xblocks = ((a.P + SKEL_Q - 1) / SKEL_Q) * ysl, n_yblocks = ((M + SKEL_Q - 1) / SKEL_Q) * xsl;
-  hipLaunchKernelGGL(skel_nearest_kernel, dim3(n_xblocks + n_yblocks), dim3(SKEL_Q), 0, s, a, n_xblocks, ysl);
-  hipLaunchKernelGGL(skel_finish_kernel, dim3(1), dim3(1024), 0, s, a, weight, loss2);
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
+  if (int rc = bone_args(a, J, S, M, parents, d_nodes, t, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  return skel_forward<true>(a, weight, loss2, (hipStream_t)stream);
 }
 
 int riggs_skeleton_projection_backward(int32_t J, int32_t S, int32_t M, const int32_t* parents, const float* d_nodes,
@@ -346,7 +318,7 @@ int riggs_skeleton_projection_backward(int32_t J, int32_t S, int32_t M, const in
                                        float* state, const float* g_loss, const float* g_weighted, float* grad_nodes,
                                        riggs_stream stream) {
   SkelProjArgs a;
-  if (int rc = skel_fill(a, J, S, M, parents, d_nodes, t, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  if (int rc = bone_args(a, J, S, M, parents, d_nodes, t, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
   RIGGS_REQUIRE((g_loss || g_weighted) && grad_nodes, "NULL buffer");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(skel_bone_grad_kernel, dim3(J - 1), dim3(256), 0, s, a, g_loss, g_weighted, weight);
@@ -364,16 +336,8 @@ int riggs_node_projection_forward(int32_t J, int32_t M, const float* d_nodes, co
                                   float cx, float cy, const float* thinned, const int32_t* pixel_count, const float* weight,
                                   float* state, float* loss2, riggs_stream stream) {
   SkelProjArgs a;
-  if (int rc = node_fill(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
-  RIGGS_REQUIRE(loss2, "NULL buffer");
-  hipStream_t s = (hipStream_t)stream;
-  RIGGS_HIP_CHECK(hipMemsetAsync(state, 0, sizeof(float) * (2 * (size_t)J + 2 * (size_t)M), s));  // zero = "no neighbour yet"
-  const int ysl = (M + SKEL_C - 1) / SKEL_C, xsl = (J + SKEL_C - 1) / SKEL_C;
-  const int n_xblocks = ((J + SKEL_Q - 1) / SKEL_Q) * ysl, n_yblocks = ((M + SKEL_Q - 1) / SKEL_Q) * xsl;
-  hipLaunchKernelGGL(node_nearest_kernel, dim3(n_xblocks + n_yblocks), dim3(SKEL_Q), 0, s, a, n_xblocks, ysl);
-  hipLaunchKernelGGL(skel_finish_kernel, dim3(1), dim3(1024), 0, s, a, weight, loss2);
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
+  if (int rc = node_args(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  return skel_forward<false>(a, weight, loss2, (hipStream_t)stream);
 }
 
 int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, const float* world_view_transform, float fx, float fy,
@@ -381,7 +345,7 @@ int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, c
                                    float* state, const float* g_loss, const float* g_weighted, float* grad_nodes,
                                    riggs_stream stream) {
   SkelProjArgs a;
-  if (int rc = node_fill(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
+  if (int rc = node_args(a, J, M, d_nodes, world_view_transform, fx, fy, cx, cy, thinned, pixel_count, state)) return rc;
   RIGGS_REQUIRE((g_loss || g_weighted) && grad_nodes, "NULL buffer");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(node_grad_kernel, dim3(J), dim3(256), 0, s, a, g_loss, g_weighted, weight, grad_nodes);

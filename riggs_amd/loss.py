@@ -193,19 +193,27 @@ def landmark_interpolate(landmarks, steps, step, interpolation='log'):
     raise NotImplementedError("unknown interpolation type: %s" % interpolation)
 
 
-# ---- skeleton projection loss (train_rig.py:309-314) ---------------------------------------------------------------------
-class _SkeletonProjection(torch.autograd.Function):
+# ---- projection losses: points of the posed skeleton against the thinned silhouette pixels (csrc/skel_loss.hip) ---------------
+def _projection_entry(d_nodes, parents, t, M):
+    """Name and leading arguments of the C entry points of a point set: samples on the bones (``parents`` and ``t`` given,
+    train_rig.py:309-314) or the nodes themselves (both None, train_gui.py:1134-1138)."""
+    if parents is None:
+        return "riggs_node_projection", (d_nodes.shape[0], M), (d_nodes.data_ptr(),)
+    return ("riggs_skeleton_projection", (d_nodes.shape[0], t.shape[0], M),
+            (parents.data_ptr(), d_nodes.data_ptr(), t.data_ptr()))
+
+
+class _Projection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d_nodes, parents, t, view, thinned, weight, count, fx, fy, cx, cy):
-        J, S, M = d_nodes.shape[0], t.shape[0], thinned.shape[0]
+        name, dims, points = _projection_entry(d_nodes, parents, t, thinned.shape[0])
         lib = L.lib()
-        n_state = lib.riggs_skeleton_projection_state_floats(J, S, M)
+        n_state = getattr(lib, name + "_state_floats")(*dims)
         state = torch.empty(max(int(n_state), 2) // 2 + 1, dtype=torch.float64, device=d_nodes.device)  # 8-byte aligned
         loss2 = torch.empty(2, dtype=torch.float32, device=d_nodes.device)
-        L.check(lib.riggs_skeleton_projection_forward(J, S, M, parents.data_ptr(), d_nodes.data_ptr(), t.data_ptr(),
-                                                      view.data_ptr(), fx, fy, cx, cy, thinned.data_ptr(), L.ptr(count),
-                                                      L.ptr(weight), state.data_ptr(), loss2.data_ptr(), L.stream_ptr()),
-                "riggs_skeleton_projection_forward")
+        L.check(getattr(lib, name + "_forward")(*dims, *points, view.data_ptr(), fx, fy, cx, cy, thinned.data_ptr(), L.ptr(count),
+                                                L.ptr(weight), state.data_ptr(), loss2.data_ptr(), L.stream_ptr()),
+                name + "_forward")
         ctx.save_for_backward(d_nodes, parents, t, view, thinned, state, weight, count)
         ctx.intr = (fx, fy, cx, cy)
         ctx.set_materialize_grads(False)
@@ -214,18 +222,16 @@ class _SkeletonProjection(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_weighted):
         d_nodes, parents, t, view, thinned, state, weight, count = ctx.saved_tensors
-        J, S, M = d_nodes.shape[0], t.shape[0], thinned.shape[0]
         if g_loss is None and g_weighted is None:
             return (None,) * 11
         f = lambda g: None if g is None else g.to(torch.float32).contiguous()  # noqa: E731
         g_loss, g_weighted = f(g_loss), f(g_weighted)
         grad = torch.empty_like(d_nodes)
-        fx, fy, cx, cy = ctx.intr
-        L.check(L.lib().riggs_skeleton_projection_backward(J, S, M, parents.data_ptr(), d_nodes.data_ptr(), t.data_ptr(),
-                                                           view.data_ptr(), fx, fy, cx, cy, thinned.data_ptr(), L.ptr(count),
-                                                           L.ptr(weight), state.data_ptr(), L.ptr(g_loss), L.ptr(g_weighted),
-                                                           grad.data_ptr(), L.stream_ptr()),
-                "riggs_skeleton_projection_backward")
+        name, dims, points = _projection_entry(d_nodes, parents, t, thinned.shape[0])
+        L.check(getattr(L.lib(), name + "_backward")(*dims, *points, view.data_ptr(), *ctx.intr, thinned.data_ptr(), L.ptr(count),
+                                                     L.ptr(weight), state.data_ptr(), L.ptr(g_loss), L.ptr(g_weighted),
+                                                     grad.data_ptr(), L.stream_ptr()),
+                name + "_backward")
         return (grad,) + (None,) * 10
 
 
@@ -252,6 +258,22 @@ def camera_intrinsics(viewpoint_cam):
     return float(fx), float(fy), W / 2, H / 2
 
 
+def _projection_inputs(viewpoint_cam, weight, pixel_count, thinned_shape):
+    """What both projection losses take besides their points, validated and normalised: ``(view, thinned, weight, pixel_count,
+    (fx, fy, cx, cy))``."""
+    thinned = L.require_cuda_f32("viewpoint_cam.thinned", viewpoint_cam.thinned).contiguous()
+    if thinned.dim() != 2 or thinned.shape[1] != 2:
+        raise L.RiggsHipError("viewpoint_cam.thinned must be %s (row, col)" % thinned_shape)
+    view = L.require_cuda_f32("viewpoint_cam.world_view_transform", viewpoint_cam.world_view_transform, (4, 4)).contiguous()
+    if weight is not None:
+        weight = L.require_cuda_f32("weight", weight).reshape(1)
+    if pixel_count is not None:
+        if not pixel_count.is_cuda or pixel_count.dtype != torch.int32:
+            raise L.RiggsHipError("pixel_count must be a CUDA(HIP) int32 scalar tensor")
+        pixel_count = pixel_count.reshape(1)
+    return view, thinned, weight, pixel_count, camera_intrinsics(viewpoint_cam)
+
+
 def cal_skeleton_loss(d_nodes, parents, viewpoint_cam, t=None, num_sample=512, weight=None, pixel_count=None):
     """``TrainRig.cal_skeleton_loss(d_nodes, viewpoint_cam)`` (/root/reference/train_rig.py:309-314) with the skeleton's
     ``parents`` passed explicitly: points sampled on the posed bones, projected with the camera (elements are (row, col)) and
@@ -268,77 +290,27 @@ def cal_skeleton_loss(d_nodes, parents, viewpoint_cam, t=None, num_sample=512, w
     if t is None:
         t = sampling_steps(d_nodes, par, num_sample)
     t = L.require_cuda_f32("t", t).contiguous()
-    thinned = L.require_cuda_f32("viewpoint_cam.thinned", viewpoint_cam.thinned).contiguous()
-    if thinned.dim() != 2 or thinned.shape[1] != 2:
-        raise L.RiggsHipError("viewpoint_cam.thinned must be (M, 2) (row, col)")
+    view, thinned, weight, pixel_count, intr = _projection_inputs(viewpoint_cam, weight, pixel_count, "(M, 2)")
     if t.shape[0] == 0 or thinned.shape[0] == 0:
         raise L.RiggsHipError("empty point set: the chamfer distance of the reference is undefined")
-    view = L.require_cuda_f32("viewpoint_cam.world_view_transform", viewpoint_cam.world_view_transform, (4, 4)).contiguous()
-    fx, fy, cx, cy = camera_intrinsics(viewpoint_cam)
-    if weight is not None:
-        weight = L.require_cuda_f32("weight", weight).reshape(1)
-    if pixel_count is not None:
-        if not pixel_count.is_cuda or pixel_count.dtype != torch.int32:
-            raise L.RiggsHipError("pixel_count must be a CUDA(HIP) int32 scalar tensor")
-        pixel_count = pixel_count.reshape(1)
-    loss, weighted = _SkeletonProjection.apply(d_nodes, par, t, view, thinned, weight, pixel_count, fx, fy, cx, cy)
+    loss, weighted = _Projection.apply(d_nodes, par, t, view, thinned, weight, pixel_count, *intr)
     return loss if weight is None else (loss, weighted)
-
-
-class _NodeProjection(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, d_nodes, view, thinned, weight, count, fx, fy, cx, cy):
-        J, M = d_nodes.shape[0], thinned.shape[0]
-        lib = L.lib()
-        n_state = lib.riggs_node_projection_state_floats(J, M)
-        state = torch.empty(max(int(n_state), 2) // 2 + 1, dtype=torch.float64, device=d_nodes.device)  # 8-byte aligned
-        loss2 = torch.empty(2, dtype=torch.float32, device=d_nodes.device)
-        L.check(lib.riggs_node_projection_forward(J, M, d_nodes.data_ptr(), view.data_ptr(), fx, fy, cx, cy, thinned.data_ptr(),
-                                                  L.ptr(count), L.ptr(weight), state.data_ptr(), loss2.data_ptr(), L.stream_ptr()),
-                "riggs_node_projection_forward")
-        ctx.save_for_backward(d_nodes, view, thinned, state, weight, count)
-        ctx.intr = (fx, fy, cx, cy)
-        ctx.set_materialize_grads(False)
-        return loss2[0], loss2[1]
-
-    @staticmethod
-    def backward(ctx, g_loss, g_weighted):
-        d_nodes, view, thinned, state, weight, count = ctx.saved_tensors
-        if g_loss is None and g_weighted is None:
-            return (None,) * 9
-        f = lambda g: None if g is None else g.to(torch.float32).contiguous()  # noqa: E731
-        g_loss, g_weighted = f(g_loss), f(g_weighted)
-        grad = torch.empty_like(d_nodes)
-        fx, fy, cx, cy = ctx.intr
-        L.check(L.lib().riggs_node_projection_backward(d_nodes.shape[0], thinned.shape[0], d_nodes.data_ptr(), view.data_ptr(), fx, fy,
-                                                       cx, cy, thinned.data_ptr(), L.ptr(count), L.ptr(weight), state.data_ptr(),
-                                                       L.ptr(g_loss), L.ptr(g_weighted), grad.data_ptr(), L.stream_ptr()),
-                "riggs_node_projection_backward")
-        return (grad,) + (None,) * 8
 
 
 def node_projection_loss(d_nodes, viewpoint_cam, weight=None, pixel_count=None):
     """The node projection term of a stage-1 iteration (/root/reference/train_gui.py:1134-1138): all M control nodes
     projected by ``project_nodes_to_2d_elements`` (utils/other_utils.py:101-127: elements are (row, col), ``K``'s principal
     point when the camera has one) against ``viewpoint_cam.thinned`` by the two-sided L1 chamfer distance with pytorch3d's
-    default reductions (mean over the points of each side, summed); differentiable w.r.t. ``d_nodes``.  Kernels of its own next
-    to the skeleton-projection ones (csrc/skel_loss.hip: the point set is the nodes themselves, no parents, no sampling steps).
+    default reductions (mean over the points of each side, summed); differentiable w.r.t. ``d_nodes``.  The implementation of
+    ``cal_skeleton_loss`` (csrc/skel_loss.hip) over another point set: the nodes themselves, no parents, no sampling steps.
     ``weight`` / ``pixel_count``: the contract of ``cal_skeleton_loss`` — with ``weight`` the pair ``(loss, weight * loss)``."""
     d_nodes = L.require_cuda_f32("d_nodes", d_nodes).contiguous()
     if d_nodes.dim() != 2 or d_nodes.shape[1] != 3 or d_nodes.shape[0] < 1:
         raise L.RiggsHipError("d_nodes must be (M >= 1, 3)")
-    thinned = L.require_cuda_f32("viewpoint_cam.thinned", viewpoint_cam.thinned).contiguous()
-    if thinned.dim() != 2 or thinned.shape[1] != 2 or thinned.shape[0] == 0:
+    view, thinned, weight, pixel_count, intr = _projection_inputs(viewpoint_cam, weight, pixel_count, "(P >= 1, 2)")
+    if thinned.shape[0] == 0:
         raise L.RiggsHipError("viewpoint_cam.thinned must be (P >= 1, 2) (row, col)")
-    view = L.require_cuda_f32("viewpoint_cam.world_view_transform", viewpoint_cam.world_view_transform, (4, 4)).contiguous()
-    fx, fy, cx, cy = camera_intrinsics(viewpoint_cam)
-    if weight is not None:
-        weight = L.require_cuda_f32("weight", weight).reshape(1)
-    if pixel_count is not None:
-        if not pixel_count.is_cuda or pixel_count.dtype != torch.int32:
-            raise L.RiggsHipError("pixel_count must be a CUDA(HIP) int32 scalar tensor")
-        pixel_count = pixel_count.reshape(1)
-    loss, weighted = _NodeProjection.apply(d_nodes, view, thinned, weight, pixel_count, fx, fy, cx, cy)
+    loss, weighted = _Projection.apply(d_nodes, None, None, view, thinned, weight, pixel_count, *intr)
     return loss if weight is None else (loss, weighted)
 
 

@@ -1,6 +1,6 @@
-"""The node projection term of stage 1 (train_gui.py:1133-1139): ``riggs_amd.loss.node_projection_loss`` — kernels and entry
-points of its own next to the skeleton-projection ones (csrc/skel_loss.hip: the bone form's kernels are textually untouched, so
-``cal_skeleton_loss`` computes what it computed) — against the reference's goldens and a float64 restatement.
+"""The node projection term of stage 1 (train_gui.py:1133-1139): ``riggs_amd.loss.node_projection_loss`` — the implementation of
+the skeleton projection loss (csrc/skel_loss.hip) over another point set, the nodes themselves — against the reference's goldens
+and a float64 restatement, and against ``cal_skeleton_loss`` on a skeleton whose sample points are the same nodes.
 
 Bounds: loss 1e-5 relative; gradient 1e-4 of its largest entry, per element."""
 import os
@@ -110,6 +110,42 @@ def test_node_projection_loss_against_float64(M, P, seed, with_K):
         l3.backward()
         assert abs(l3.item() - want_c) <= 1e-5 * want_c
         assert np.abs(x3.grad.cpu().numpy() - g_c).max() <= 1e-4 * np.abs(g_c).max()
+
+
+# a star skeleton sampled at t = 1 puts the bone form's points (1 child + 0 root) on joints 1..J-1 exactly: both forms then run
+# the same point set through the same nearest-neighbour, reduction and point-gradient code.  One point, one pixel; one past a
+# 64-query block and a 256-candidate slice in both directions; several blocks with a K camera; pixel_count; weight.
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,M,seed,with_K,counted,weighted", [(1, 1, 11, False, False, False), (65, 257, 12, False, False, False),
+                                                              (300, 40, 13, True, False, False), (65, 257, 14, False, True, False),
+                                                              (300, 40, 15, True, False, True)])
+def test_bone_form_on_a_star_skeleton_is_the_node_form(P, M, seed, with_K, counted, weighted):
+    from riggs_amd.loss import cal_skeleton_loss, node_projection_loss
+    nodes, z = _random_case(P + 1, M, seed, with_K)
+    cam = _Cam(z)
+    kw = {}
+    if counted:
+        kw["pixel_count"] = torch.tensor(M - M // 3, dtype=torch.int32, device="cuda")
+    if weighted:
+        kw["weight"] = torch.tensor(0.37, device="cuda")
+    xb = torch.from_numpy(nodes).cuda().requires_grad_(True)
+    xn = torch.from_numpy(nodes).cuda().requires_grad_(True)
+    lb = cal_skeleton_loss(xb, torch.zeros(P + 1, dtype=torch.int32), cam, t=torch.tensor([1.0], device="cuda"), **kw)
+    ln = node_projection_loss(xn[1:], cam, **kw)
+    if weighted:
+        assert torch.equal(lb[0], ln[0]) and torch.equal(lb[1], ln[1])
+        lb, ln = lb[0] + lb[1], ln[0] + ln[1]
+    else:
+        assert torch.equal(lb, ln)
+    lb.backward()
+    ln.backward()
+    gb, gn = xb.grad.cpu().numpy(), xn.grad.cpu().numpy()
+    bound = 1e-4 * np.abs(gn).max()
+    print("P", P, "M", M, "loss", lb.item(), "largest |bone - node| gradient", np.abs(gb[1:] - gn[1:]).max(), "root", np.abs(gb[0]).max(),
+          "bound", bound)
+    assert np.all(gn[0] == 0)  # (the slice's own backward: joint 0 is no node of the node form)
+    assert np.abs(gb[1:] - gn[1:]).max() <= bound
+    assert np.abs(gb[0]).max() <= bound
 
 
 @pytest.mark.gpu
