@@ -968,6 +968,19 @@ int riggs_mlp_embed(int32_t N, int32_t multires, int32_t n_tail, const float* x,
 /* self-test of the MFMA fragment layouts mlp.hip assumes: writes D = A B for A = [I_16; 0] and an asymmetric B */
 int riggs_mlp_layout_probe(float* out32x32, riggs_stream stream);
 
+/* Farthest-point sampling (csrc/fps.hip; utils/time_utils.py:461-482, bit for bit: nearest starts at 1e10, squared distance
+ * fl(fl(dx dx + dy dy) + dz dz) without fused multiply-add, update on dist < nearest, next point = the maximum of nearest with
+ * the LOWEST index on ties, the start index first in the output).  xyz: N rows of 3 fp32, row_stride floats apart (>= 3);
+ * start: one device int64, read by the first launch (clamped to [0, N)): nothing synchronises; workspace:
+ * riggs_fps_workspace_bytes(N) bytes, 256-byte aligned, contents irrelevant (nearest and the per-workgroup partials);
+ * out_indices: npoint device int64.  One plain launch per picked point over riggs_fps_blocks(N) workgroups (sized from N: one
+ * workgroup up to 1024 points); no grid barrier, no cooperative launch.  npoint may exceed N (the sweep then repeats indices as
+ * the reference does). */
+int32_t riggs_fps_blocks(int32_t N);
+size_t riggs_fps_workspace_bytes(int32_t N);
+int riggs_fps_sample(int32_t N, int32_t npoint, const float* xyz, int64_t row_stride, const int64_t* start, void* workspace,
+                     int64_t* out_indices, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

@@ -272,6 +272,9 @@ _SIGS = {
     "riggs_node_mlp_backward_workspace_floats": (C.c_size_t, [C.c_int32] * 3),
     "riggs_node_mlp_forward": (C.c_int, [C.POINTER(NodeMlp), C.c_int32, _P, _P, C.c_int32] + [_P] * 7),
     "riggs_node_mlp_backward": (C.c_int, [C.POINTER(NodeMlp), C.c_int32] + [_P] * 7 + [C.POINTER(NodeMlpGrads), _P]),
+    "riggs_fps_blocks": (C.c_int32, [C.c_int32]),
+    "riggs_fps_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "riggs_fps_sample": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
 }
 
 

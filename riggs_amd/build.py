@@ -37,6 +37,7 @@ SOURCES = {
     "node_reg.hip": ["-ffp-contract=off"],
     "node_mlp.hip": ["-ffp-contract=off"],
     "flow.hip": ["-ffp-contract=off"],  # (the loss forms fl(w c) - fl(w m) as the reference does: no fused multiply-subtract)
+    "fps.hip": ["-ffp-contract=off"],  # (the squared distance is fl(fl(dx dx + dy dy) + dz dz), as torch.sum gives it on the CPU)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -71,7 +71,17 @@ def strip_symmetric(m):  # upper triangle xx xy xz yy yz zz: utils/general_utils
 
 def farthest_point_sample(xyz, npoint, start=None):
     """(B, N, C) -> (B, npoint) indices of an iterative farthest-point sweep from a random start
-    (utils/time_utils.py:461-482); ``start`` (B,) fixes the first index."""
+    (utils/time_utils.py:461-482); ``start`` (B,) fixes the first index.  One fp32 cloud of 3-vectors on the device goes to
+    the kernel (riggs_amd/fps.py: one launch per point); every other input keeps the torch loop."""
+    B, N, C = xyz.shape
+    if xyz.is_cuda and xyz.dtype is torch.float32 and B == 1 and C == 3 and N >= 1:
+        from .fps import farthest_point_sample as fps_hip
+        return fps_hip(xyz, npoint, start=start)
+    return farthest_point_sample_torch(xyz, npoint, start)
+
+
+def farthest_point_sample_torch(xyz, npoint, start=None):
+    """The sweep as torch ops, about eight launches per point: CPU tensors, batches, C != 3, other dtypes."""
     B, N, _ = xyz.shape
     dev = xyz.device
     picked = torch.zeros(B, npoint, dtype=torch.long, device=dev)
