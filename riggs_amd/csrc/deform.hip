@@ -2,9 +2,16 @@
 //   fk_*   : forward kinematics over <= 64 joints on ONE wave64, <= 256 on one workgroup (replaces ~3*J torch
 //            launches of SkeletonWarp.chain_product_transform, skeleton_warp.py:242-273)
 //   lbs_*  : bone-distance skinning weights + linear blend skinning fused per Gaussian, with the
-//            <= 63 (<= 255: the *_wide kernels) bone records (segment, radius, 3x4 transform, quaternion) staged in LDS.
+//            <= 63 (<= 255: the MAX_J_WIDE instantiations) bone records (segment, radius, 3x4 transform, quaternion) staged in LDS.
+// The skinning forward is ONE template over the joint capacity (MAX_J / MAX_J_WIDE) and the form of the top-K selection set
+// (SelReg / SelLds), with one topk_select and one topk_emit_ascending.  Where the same lines still stand in several kernels (the
+// chain's write-out in its four kernels, the accumulate step and the write-out of the LDS and the scalar forward, the walk of the
+// two bone-lane backwards, the top-K backward on either side of 64 joints) a shared form changed the compiler's output for a
+// kernel on the benchmark's path, or measured slower: NOTES.md "deform: one body per step".
 // Backward reduces over the N Gaussians inside the kernel: wave64 DPP sums -> LDS -> one atomic
 // per workgroup per output.
+#include <type_traits>
+
 #include "fk_device.h"
 
 namespace riggs {
@@ -82,7 +89,7 @@ struct LbsArgs {
   // backward
   const float *g_xyz, *g_rot;
   float *dG, *drho, *dgt, *dmask;
-  float* partial;  // [workgroups][(J-1)*13 + 3] per-workgroup sums (deterministic two-stage reduction)
+  float* partial;  // [workgroups][(J-1)*13 + 3] per-workgroup sums (two-stage reduction; the second stage runs in a fixed order)
   // forward with the kinematic chain inside (riggs_lbs_forward_fk): the pose, and where workgroup 0 leaves the chain's results
   const float* local_rot;
   float *fk_transforms, *fk_node_rot, *fk_d_nodes;
@@ -138,34 +145,87 @@ __device__ __forceinline__ float bone_d2_fast(const Bone& b, float px, float py,
   return sx * sx + sy * sy + sz * sz;
 }
 
-// Top-K selection (K > 0): bitmask of the K bones with the smallest (d2, index), found by K
-// selection passes over the <= 63 bones.  Already-picked bones are excluded through the mask, so
+// The selection set of the top-K configuration (K > 0), one per thread, in two forms with one interface:
+//   <= 64 joints: a 64-bit mask in registers;
+//   <= 256 joints: 256 bits as a column of an LDS array (word w of thread t at col[w][t]: conflict-free).  A walk over
+//   k = 0, 1, .. reloads the 32-bit word where k enters it ((k & 31) == 0): test() is for such ascending walks.
+struct SelReg {
+  static constexpr bool in_lds = false;
+  uint64_t m;
+  __device__ __forceinline__ void clear() { m = 0; }
+  __device__ __forceinline__ bool test(int k) { return (m >> k) & 1ull; }
+  __device__ __forceinline__ void set(int k) { m |= 1ull << k; }
+  __device__ __forceinline__ void reset(int k) { m &= ~(1ull << k); }
+};
+struct SelLds {
+  static constexpr bool in_lds = true;
+  typedef uint32_t Column[FK_WIDE_WORDS][256];
+  uint32_t (*col)[256];
+  uint32_t w;
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int i = 0; i < FK_WIDE_WORDS; i++) col[i][threadIdx.x] = 0u;
+    w = 0u;
+  }
+  __device__ __forceinline__ bool test(int k) {
+    if ((k & 31) == 0) w = col[k >> 5][threadIdx.x];
+    return (w >> (k & 31)) & 1u;
+  }
+  __device__ __forceinline__ void set(int k) { col[k >> 5][threadIdx.x] |= 1u << (k & 31); }
+  __device__ __forceinline__ void reset(int k) { col[k >> 5][threadIdx.x] &= ~(1u << (k & 31)); }
+};
+
+// Top-K selection (K > 0): the set of the K bones with the smallest (d2, index), found by K
+// selection passes over the bones.  Already-picked bones are excluded through the set, so
 // no floating-point value is ever compared for equality across call sites.
-__device__ __forceinline__ uint64_t topk_mask(const Bone* bones, int B, int K, float px, float py, float pz) {
-  uint64_t mask = 0;
+template <class Sel>
+__device__ __forceinline__ void topk_select(Sel& sel, const Bone* bones, int B, int K, float px, float py, float pz) {
+  sel.clear();
   for (int s = 0; s < K; s++) {
     float best = INFINITY;
     int bi = -1;
     for (int k = 0; k < B; k++) {
-      if ((mask >> k) & 1ull) continue;
+      if (sel.test(k)) continue;
       const float d2 = bone_d2(bones[k], px, py, pz);
       if (d2 < best || bi < 0) { best = d2; bi = k; }
     }
-    mask |= 1ull << bi;
+    sel.set(bi);
   }
-  return mask;
+}
+// nn_weight / nn_idx of Gaussian n in ascending-d2 order like torch.topk(largest=False): K selection passes inside the set
+// (cleared as they go)
+template <class Sel>
+__device__ __forceinline__ void topk_emit_ascending(Sel& sel, const Bone* bones, int B, int K, float px, float py, float pz,
+                                                    float inv, int n, float* nn_weight, int64_t* nn_idx) {
+  for (int s = 0; s < K; s++) {
+    float best = INFINITY; int bi = -1;
+    for (int k = 0; k < B; k++) {
+      if (!sel.test(k)) continue;
+      const float d2 = bone_d2(bones[k], px, py, pz);
+      if (d2 < best || bi < 0) { best = d2; bi = k; }
+    }
+    sel.reset(bi);
+    if (nn_weight) nn_weight[(size_t)n * K + s] = (fast_exp(-best * bones[bi].inv2r2) + 1e-7f) * inv;
+    if (nn_idx) nn_idx[(size_t)n * K + s] = bi + 1;
+  }
 }
 
 #define LBS_PTS2_MIN_N 1000000
 #define LBS_PTS2_MIN_J 16
 // FK: the workgroup runs the kinematic chain itself (fk_device.h: ~1 us on its first wave, against a launch of its own in front
 // of this one — every workgroup repeats it, workgroup 0 keeps the results)
-template <bool TOPK, bool FK, int PTS>
+// MAXJ = MAX_J_WIDE: skeletons of 65..256 joints — up to 255 bone records in LDS and the selection set there too; the chain is a
+// launch of its own in front (riggs_lbs_forward_fk), one Gaussian per thread, weight_mod read from global memory
+template <bool TOPK, bool FK, int PTS, int MAXJ = MAX_J>
 __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
-  __shared__ Bone bones[MAX_J - 1];
+  constexpr bool WIDE = MAXJ > MAX_J;
+  constexpr bool MOD_TILE = !WIDE && PTS == 1;
+  static_assert(!TOPK || PTS == 1, "the top-K path takes one Gaussian per thread");
+  static_assert(!WIDE || (!FK && PTS == 1 && !MOD_TILE), "beyond 64 joints: no chain inside, one Gaussian per thread, no weight_mod tile");
+  typedef std::conditional_t<WIDE && TOPK, SelLds, SelReg> Sel;
+  __shared__ Bone bones[MAXJ - 1];
   // (the Gaussians' positions first: their round trip runs under the chain and the staging — the compiler keeps loads behind
   // the barriers where it finds them)
-  static_assert(!TOPK || PTS == 1, "the top-K path takes one Gaussian per thread");
   const int n0 = blockIdx.x * (256 * PTS) + threadIdx.x;
   float px[PTS], py[PTS], pz[PTS];
   bool on[PTS];
@@ -180,18 +240,22 @@ __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
   // instructions of 64 addresses 4 B bytes apart each (46 lines per instruction, the L1 thrashes: +20 us on this kernel).  The
   // wave's 64 rows are one contiguous run: copied once, coalesced, into a wave-private LDS tile (row stride odd: a column
   // read is conflict-free), where the bone loop reads them.  (a.mod_lds: the launch reserved 256 (B | 1) floats)
-  extern __shared__ float s_mod_dyn[];
-  const int BP = (a.J - 1) | 1;
-  float* s_mod = s_mod_dyn + (threadIdx.x >> 6) * 64 * BP;
-  if (PTS == 1 && a.mod_lds) {
-    const int Bm = a.J - 1, lane_ = threadIdx.x & 63;
-    const int ng = blockIdx.x * 256 + (threadIdx.x & ~63);
-    const int n_el = max(0, min(64, a.N - ng)) * Bm;
-    const float* run = a.weight_mod + (size_t)ng * Bm;
-    const float invB = 1.0f / (float)Bm;
-    for (int e = lane_; e < n_el; e += 64) {
-      const int r = (int)(((float)e + 0.5f) * invB);
-      s_mod[r * BP + (e - r * Bm)] = run[e];
+  [[maybe_unused]] float* s_mod = nullptr;
+  [[maybe_unused]] int BP = 0;
+  if constexpr (MOD_TILE) {
+    extern __shared__ float s_mod_dyn[];
+    BP = (a.J - 1) | 1;
+    s_mod = s_mod_dyn + (threadIdx.x >> 6) * 64 * BP;
+    if (a.mod_lds) {
+      const int Bm = a.J - 1, lane_ = threadIdx.x & 63;
+      const int ng = blockIdx.x * 256 + (threadIdx.x & ~63);
+      const int n_el = max(0, min(64, a.N - ng)) * Bm;
+      const float* run = a.weight_mod + (size_t)ng * Bm;
+      const float invB = 1.0f / (float)Bm;
+      for (int e = lane_; e < n_el; e += 64) {
+        const int r = (int)(((float)e + 0.5f) * invB);
+        s_mod[r * BP + (e - r * Bm)] = run[e];
+      }
     }
   }
   if constexpr (FK) {
@@ -238,7 +302,12 @@ __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
   // workgroup instead of once per block — are slower: 17.5 -> 19.7 -> 24.6 us at 1172 / 586 / 293 workgroups)
   const int B = a.J - 1;
   if (n0 >= a.N) return;
-  const uint64_t selmask = TOPK ? topk_mask(bones, B, a.K, px[0], py[0], pz[0]) : ~0ull;
+  Sel sel;
+  if constexpr (Sel::in_lds) {
+    __shared__ typename Sel::Column s_sel;
+    sel.col = s_sel;
+  }
+  if (TOPK) topk_select(sel, bones, B, a.K, px[0], py[0], pz[0]);
   float M[PTS][12], qa[PTS][4], sum[PTS];
 #pragma unroll
   for (int p = 0; p < PTS; p++) {
@@ -250,12 +319,12 @@ __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
   }
   for (int k = 0; k < B; k++) {
     const Bone& b = bones[k];
-    if (TOPK && !((selmask >> k) & 1ull)) continue;
+    if (TOPK && !sel.test(k)) continue;
 #pragma unroll
     for (int p = 0; p < PTS; p++) {
       const float d2 = TOPK ? bone_d2(b, px[p], py[p], pz[p]) : bone_d2_fast(b, px[p], py[p], pz[p]);
       float u = fast_exp(-d2 * b.inv2r2);                // skeleton_warp.py:66
-      if (a.weight_mod) u *= (PTS == 1 && a.mod_lds) ? s_mod[(threadIdx.x & 63) * BP + k]
+      if (a.weight_mod) u *= (MOD_TILE && a.mod_lds) ? s_mod[(threadIdx.x & 63) * BP + k]
                                                      : a.weight_mod[(size_t)(on[p] ? n0 + 256 * p : n0) * B + k];  // :68-69
       const float v = u + 1e-7f;                          // :71
       sum[p] += v;
@@ -279,19 +348,7 @@ __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
     reinterpret_cast<float4*>(a.d_rot)[n] = make_float4(qa[p][0] * inv * m, qa[p][1] * inv * m, qa[p][2] * inv * m, qa[p][3] * inv * m);
     if (a.nn_weight || a.nn_idx) {
       if (TOPK) {
-        // ascending-d2 order like torch.topk(largest=False): K selection passes inside the mask
-        uint64_t left = selmask;
-        for (int s = 0; s < a.K; s++) {
-          float best = INFINITY; int bi = -1;
-          for (int k = 0; k < B; k++) {
-            if (!((left >> k) & 1ull)) continue;
-            const float d2 = bone_d2(bones[k], px[p], py[p], pz[p]);
-            if (d2 < best || bi < 0) { best = d2; bi = k; }
-          }
-          left &= ~(1ull << bi);
-          if (a.nn_weight) a.nn_weight[(size_t)n * a.K + s] = (fast_exp(-best * bones[bi].inv2r2) + 1e-7f) * inv;
-          if (a.nn_idx) a.nn_idx[(size_t)n * a.K + s] = bi + 1;
-        }
+        topk_emit_ascending(sel, bones, B, a.K, px[p], py[p], pz[p], inv, n, a.nn_weight, a.nn_idx);
       } else {
         for (int k = 0; k < B; k++) {
           if (a.nn_weight) a.nn_weight[(size_t)n * B + k] = (fast_exp(-bone_d2_fast(bones[k], px[p], py[p], pz[p]) * bones[k].inv2r2) *
@@ -409,10 +466,12 @@ __global__ __launch_bounds__(256) void lbs_forward_scalar_kernel(LbsArgs a, cons
 // drho_k = sum_n dL/dv_nk * u_nk * d2_nk * exp(-2 rho_k).
 // This thread-per-Gaussian kernel serves the top-K configuration (K > 0, skeleton_warp.py:46-49: every Gaussian has its
 // own bone subset); the all-bones default (K = -1) runs the bone-lane kernel below.
+// (K > 0 is required: with K <= 0 the selection would be empty.  The host launches it for K > 0 only.)
 __global__ __launch_bounds__(256) void lbs_backward_kernel(LbsArgs a) {
   __shared__ Bone bones[MAX_J - 1];
   __shared__ float s_acc[MAX_J - 1][13];
   __shared__ float s_gt[3];
+  SelReg sel;
   stage_bones(a, bones);
   const int B = a.J - 1;
   for (int e = threadIdx.x; e < B * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
@@ -433,13 +492,13 @@ __global__ __launch_bounds__(256) void lbs_backward_kernel(LbsArgs a) {
   const float gh[3] = {g[0] * m, g[1] * m, g[2] * m};
   const float hh4[4] = {h[0] * m, h[1] * m, h[2] * m, h[3] * m};
   // pass 1: normaliser and blended outputs
-  const uint64_t selmask = a.K > 0 ? topk_mask(bones, B, a.K, px, py, pz) : ~0ull;
+  topk_select(sel, bones, B, a.K, px, py, pz);
   float M[12], qa[4] = {0.f, 0.f, 0.f, 0.f}, sum = 0.f;
 #pragma unroll
   for (int e = 0; e < 12; e++) M[e] = 0.f;
   for (int k = 0; k < B; k++) {
     const Bone& b = bones[k];
-    if (!((selmask >> k) & 1ull)) continue;
+    if (!sel.test(k)) continue;
     const float d2 = bone_d2(b, px, py, pz);
     const float v = fast_exp(-d2 * b.inv2r2) + 1e-7f;
     sum += v;
@@ -464,11 +523,11 @@ __global__ __launch_bounds__(256) void lbs_backward_kernel(LbsArgs a) {
   const float P[12] = {gh[0] * px, gh[0] * py, gh[0] * pz, gh[0], gh[1] * px, gh[1] * py, gh[1] * pz, gh[1],
                        gh[2] * px, gh[2] * py, gh[2] * pz, gh[2]};
   for (int k = 0; k < B; k++) {
+    const bool sel_k = sel.test(k);
     const Bone& b = bones[k];
     const float d2 = bone_d2(b, px, py, pz);
     float w = 0.f, r = 0.f;
-    const bool sel = valid && ((selmask >> k) & 1ull);
-    if (sel) {
+    if (valid && sel_k) {
       const float u = fast_exp(-d2 * b.inv2r2);
       w = (u + 1e-7f) * inv;
       const float Ax = b.G[0] * px + b.G[1] * py + b.G[2] * pz + b.G[3];
@@ -519,6 +578,21 @@ __device__ __forceinline__ float row8_sum(float v) {
   return v;
 }
 
+// The prologue of the <= 64-joint kernel (one walk) and of the 65..256-joint one (passes of LBW_PASS blocks):
+// stage the bones; padding bones up to nb blocks (never selected); zero the workgroup's sums
+__device__ __forceinline__ void lbs_bonelane_prologue(const LbsArgs& a, Bone* bones, float (*s_acc)[13], float* s_gt, int nb) {
+  const int B = a.J - 1;
+  stage_bones(a, bones);
+  for (int k = B + threadIdx.x; k < nb * LB_BONES; k += 256) {  // padding bones: never selected
+    Bone z;
+    memset(&z, 0, sizeof(z));
+    z.len2c = 1.f;
+    bones[k] = z;
+  }
+  for (int e = threadIdx.x; e < nb * LB_BONES * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
+  if (threadIdx.x < 3) s_gt[threadIdx.x] = 0.f;
+  __syncthreads();
+}
 template <int NBLK, bool MOD, int GPB>
 __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
   __shared__ Bone bones[MAX_J - 1 + LB_BONES];
@@ -553,16 +627,7 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
     }
   };
   request(0);
-  stage_bones(a, bones);
-  for (int k = B + threadIdx.x; k < NBLK * LB_BONES; k += 256) {  // padding bones: never selected
-    Bone z;
-    memset(&z, 0, sizeof(z));
-    z.len2c = 1.f;
-    bones[k] = z;
-  }
-  for (int e = threadIdx.x; e < NBLK * LB_BONES * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
-  if (threadIdx.x < 3) s_gt[threadIdx.x] = 0.f;
-  __syncthreads();
+  lbs_bonelane_prologue(a, bones, s_acc, s_gt, NBLK);
   float acc[NBLK][13];
 #pragma unroll
   for (int bb = 0; bb < NBLK; bb++)
@@ -700,7 +765,10 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
   gt0 = wave_sum(gt0); gt1 = wave_sum(gt1); gt2 = wave_sum(gt2);
   if (lane == 63) { atomicAdd(&s_gt[0], gt0); atomicAdd(&s_gt[1], gt1); atomicAdd(&s_gt[2], gt2); }
   __syncthreads();
-  // per-workgroup partial sums; lbs_backward_finish_kernel adds them up in a fixed order (deterministic)
+  // per-workgroup partial sums; lbs_backward_finish_kernel adds them up in a fixed order.  (The partial itself is not
+  // run-to-run reproducible to the bit: the workgroup's four waves add into s_acc / s_gt with LDS atomics in the order they
+  // arrive, so from three contributing waves on (N > 512) the last place of dG / drho / dgt depends on timing — measured on
+  // the MI355X, NOTES.md.  A fixed order here would need a slot per wave in LDS.)
   float* part = a.partial + (size_t)blockIdx.x * (B * 13 + 3);
   for (int e = threadIdx.x; e < B * 13; e += 256) part[e] = (&s_acc[0][0])[e];
   if (threadIdx.x < 3) part[B * 13 + threadIdx.x] = s_gt[threadIdx.x];
@@ -747,9 +815,10 @@ static void launch_lbs_bwd_bonelane(const LbsArgs& a, hipStream_t s) {
 }
 
 // ==================================================================================== skeletons of 65..256 joints
-// Separate kernels, so the <= 64-joint ones keep their LDS footprint, registers and occupancy: the chain on one workgroup
-// (fk_device.h: fk_block_*), up to 255 bone records in LDS, the top-K selection mask as 256 bits per thread in LDS, and the
-// bone-lane backward walking the bones in passes of 64.
+// The chain on one workgroup (fk_device.h: fk_block_*), and the bone-lane backward walking the bones in passes of 64, are
+// kernels of their own, and so is the top-K backward; the skinning forward is the MAX_J_WIDE instantiation of the template above
+// (up to 255 bone records in LDS, the top-K selection set as 256 bits per thread in LDS: SelLds).  The <= 64-joint
+// instantiations keep their LDS footprint, registers and occupancy.
 #define MAX_B_WIDE (MAX_J_WIDE - 1)
 
 __global__ __launch_bounds__(256) void fk_forward_wide_kernel(int J, const float* __restrict__ local_rot,
@@ -761,7 +830,7 @@ __global__ __launch_bounds__(256) void fk_forward_wide_kernel(int J, const float
   __shared__ FkWideShared sh;
   const int j = threadIdx.x;
   FkIn in;
-  fk_load_joint(j, J, local_rot, joints, parents, nullptr, nullptr, in, nullptr);
+  fk_load_joint(j, J, local_rot, joints, parents, nullptr, nullptr, in);
   FkWide f;
   fk_block_forward(J, in, f, sh);
   if (j < J) {
@@ -791,7 +860,7 @@ __global__ __launch_bounds__(256) void fk_backward_wide_kernel(int J, const floa
   __shared__ FkWideShared sh;
   const int j = threadIdx.x;
   FkIn in;
-  fk_load_joint(j, J, local_rot, joints, parents, dL_dG_in, dL_dnodes, in, nullptr);
+  fk_load_joint(j, J, local_rot, joints, parents, dL_dG_in, dL_dnodes, in);
   FkWide f;
   fk_block_forward(J, in, f, sh);
   if (dL_dnodes && j < 3) {  // d_nodes = posed + global_trans
@@ -809,7 +878,7 @@ __global__ __launch_bounds__(256) void fk_backward_wide_kernel(int J, const floa
 
 // topk_mask over up to 255 bones: the same K passes in the same (d2, index) order, the thread's 256-bit mask a column of
 // `sel` in LDS (word w of thread t at sel[w][t]: conflict-free)
-typedef uint32_t SelWide[FK_WIDE_WORDS][256];
+typedef SelLds::Column SelWide;
 __device__ __forceinline__ void topk_mask_wide(const Bone* bones, int B, int K, float px, float py, float pz, SelWide& sel) {
   const int t = threadIdx.x;
 #pragma unroll
@@ -828,73 +897,10 @@ __device__ __forceinline__ void topk_mask_wide(const Bone* bones, int B, int K, 
   }
 }
 
-// lbs_forward_kernel<TOPK, false, 1> for J > 64 (riggs_lbs_forward_fk runs the chain as a launch of its own in front)
-template <bool TOPK>
-__global__ __launch_bounds__(256) void lbs_forward_wide_kernel(LbsArgs a) {
-  __shared__ Bone bones[MAX_B_WIDE];
-  __shared__ SelWide s_sel;
-  const int t = threadIdx.x;
-  const int n = blockIdx.x * 256 + t;
-  const bool on = n < a.N;
-  const int nn = min(n, a.N - 1);
-  const float px = a.x[3 * nn], py = a.x[3 * nn + 1], pz = a.x[3 * nn + 2];
-  stage_bones(a, bones);
-  if (!on) return;
-  const int B = a.J - 1;
-  if (TOPK) topk_mask_wide(bones, B, a.K, px, py, pz, s_sel);
-  float M[12], qa[4] = {0.f, 0.f, 0.f, 0.f}, sum = 0.f;
-#pragma unroll
-  for (int e = 0; e < 12; e++) M[e] = 0.f;
-  uint32_t m = 0u;
-  for (int k = 0; k < B; k++) {
-    if (TOPK) {
-      if ((k & 31) == 0) m = s_sel[k >> 5][t];
-      if (!((m >> (k & 31)) & 1u)) continue;
-    }
-    const Bone& b = bones[k];
-    const float d2 = TOPK ? bone_d2(b, px, py, pz) : bone_d2_fast(b, px, py, pz);
-    float u = fast_exp(-d2 * b.inv2r2);                            // skeleton_warp.py:66
-    if (a.weight_mod) u *= a.weight_mod[(size_t)n * B + k];        // :68-69
-    const float v = u + 1e-7f;                                     // :71
-    sum += v;
-#pragma unroll
-    for (int e = 0; e < 12; e++) M[e] += v * b.G[e];
-#pragma unroll
-    for (int e = 0; e < 4; e++) qa[e] += v * b.q[e];
-  }
-  const float gx = a.global_trans[0], gy = a.global_trans[1], gz = a.global_trans[2];
-  const float inv = 1.0f / sum;
-  const float mm = a.motion_mask ? a.motion_mask[n] : 1.0f;
-  const float ax = (M[0] * px + M[1] * py + M[2] * pz + M[3]) * inv + gx;
-  const float ay = (M[4] * px + M[5] * py + M[6] * pz + M[7]) * inv + gy;
-  const float az = (M[8] * px + M[9] * py + M[10] * pz + M[11]) * inv + gz;
-  a.d_xyz[3 * n] = (ax - px) * mm; a.d_xyz[3 * n + 1] = (ay - py) * mm; a.d_xyz[3 * n + 2] = (az - pz) * mm;
-  reinterpret_cast<float4*>(a.d_rot)[n] = make_float4(qa[0] * inv * mm, qa[1] * inv * mm, qa[2] * inv * mm, qa[3] * inv * mm);
-  if (!a.nn_weight && !a.nn_idx) return;
-  if (TOPK) {
-    // ascending-d2 order like torch.topk(largest=False): K selection passes inside the mask (cleared as they go)
-    for (int s = 0; s < a.K; s++) {
-      float best = INFINITY; int bi = -1;
-      for (int k = 0; k < B; k++) {
-        if ((k & 31) == 0) m = s_sel[k >> 5][t];
-        if (!((m >> (k & 31)) & 1u)) continue;
-        const float d2 = bone_d2(bones[k], px, py, pz);
-        if (d2 < best || bi < 0) { best = d2; bi = k; }
-      }
-      s_sel[bi >> 5][t] &= ~(1u << (bi & 31));
-      if (a.nn_weight) a.nn_weight[(size_t)n * a.K + s] = (fast_exp(-best * bones[bi].inv2r2) + 1e-7f) * inv;
-      if (a.nn_idx) a.nn_idx[(size_t)n * a.K + s] = bi + 1;
-    }
-  } else {
-    for (int k = 0; k < B; k++) {
-      if (a.nn_weight) a.nn_weight[(size_t)n * B + k] = (fast_exp(-bone_d2_fast(bones[k], px, py, pz) * bones[k].inv2r2) *
-                                                            (a.weight_mod ? a.weight_mod[(size_t)n * B + k] : 1.0f) + 1e-7f) * inv;
-      if (a.nn_idx) a.nn_idx[(size_t)n * B + k] = k + 1;
-    }
-  }
-}
-
-// lbs_backward_kernel (top-K, thread per Gaussian) for J > 64
+// lbs_backward_kernel (top-K, thread per Gaussian) for J > 64: a kernel of its own, with its own K selection passes.  As the
+// LDS-column instantiation of one template with lbs_backward_kernel (SelLds, topk_select) it measured 0.9 % slower on the
+// MI355X at 128 and 256 joints (300 k Gaussians, K = 3: 592.6 -> 597.9 us, 1106.5 -> 1116.6 us, outside the spread of
+// five repeats), so the two stay apart.
 __global__ __launch_bounds__(256) void lbs_backward_wide_kernel(LbsArgs a) {
   __shared__ Bone bones[MAX_B_WIDE];
   __shared__ float s_acc[MAX_B_WIDE][13];
@@ -1008,16 +1014,7 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_wide_kernel(LbsArgs
   const int slot = lane >> 3, bl = lane & 7;
   const int wave_first = blockIdx.x * GPB + wave * (GPB / 4);
   const int wave_end = min(a.N, wave_first + GPB / 4);
-  stage_bones(a, bones);
-  for (int k = B + threadIdx.x; k < nblk * LB_BONES; k += 256) {  // padding bones: never selected
-    Bone z;
-    memset(&z, 0, sizeof(z));
-    z.len2c = 1.f;
-    bones[k] = z;
-  }
-  for (int e = threadIdx.x; e < nblk * LB_BONES * 13; e += 256) (&s_acc[0][0])[e] = 0.f;
-  if (threadIdx.x < 3) s_gt[threadIdx.x] = 0.f;
-  __syncthreads();
+  lbs_bonelane_prologue(a, bones, s_acc, s_gt, nblk);
   // the wave's Gaussians with an incoming gradient, listed (the others: zeros of the per-Gaussian outputs)
   int n_work = 0;
 #pragma unroll 1
@@ -1166,6 +1163,63 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_wide_kernel(LbsArgs
 
 using namespace riggs;
 
+static int fill_lbs(LbsArgs& a, int32_t N, int32_t J, int32_t K, const float* x, const float* joints,
+                    const int32_t* parents, const float* rho, const float* transforms, const float* node_rot,
+                    const float* gt, const float* mask) {
+  RIGGS_REQUIRE(J >= 2 && J <= MAX_J_WIDE, "num_joints must be in [2, 256]");
+  RIGGS_REQUIRE(N >= 0, "num_points < 0");
+  RIGGS_REQUIRE(K < J, "K must be < num_joints");
+  memset(&a, 0, sizeof(a));
+  a.N = N; a.J = J; a.K = K; a.x = x; a.joints = joints; a.parents = parents; a.node_radius_log = rho;
+  a.transforms = transforms; a.node_rot = node_rot; a.global_trans = gt; a.motion_mask = mask;
+  return 0;
+}
+
+// two Gaussians per thread in the all-bones forward (see lbs_forward_kernel) where the launch still fills the chip
+static bool lbs_two_per_thread(int N, int J) { return N >= LBS_PTS2_MIN_N && J >= LBS_PTS2_MIN_J; }
+
+static unsigned lbs_grid(int N, int pts) { return (unsigned)((N + 256 * pts - 1) / (256 * pts)); }
+// The bone records through the scalar cache (lbs_forward_scalar_kernel) where that wins: the large, many-joint scenes whose loop is
+// bound by the LDS handing every wave the records (2 M x 64: 129 -> 104 us; at 300 k x 24 the extra one-workgroup launch in front
+// costs what the loop gains: 13.0 against 15.9 us — tools/lbs_scalar_ab.py); the caller must have handed over a table
+// (riggs_lbs_bone_table_bytes).  riggs_set_option("lbs_scalar", 1) forces it at every size (the A/B), -1 forbids it.
+static bool lbs_use_scalar(const LbsArgs& a, const void* bone_table) {
+  if (!bone_table || a.K > 0 || a.weight_mod) return false;
+  const int o = option(OPT_LBS_SCALAR);
+  return o > 0 || (o == 0 && lbs_two_per_thread(a.N, a.J));
+}
+// the forward's weight_mod tile (one Gaussian per thread, up to 47 bones: 48 KB; beyond, the rows are read from global memory)
+static size_t lbs_mod_lds(LbsArgs& a, int pts) {
+  a.mod_lds = (a.weight_mod && pts == 1 && a.J - 1 <= 47) ? 1 : 0;
+  return a.mod_lds ? (size_t)256 * ((a.J - 1) | 1) * sizeof(float) : 0;
+}
+
+// The forward's launches, FK: with the kinematic chain inside (the <= 64-joint forms; beyond, the caller has run it in front).
+// Wide, then the scalar table, then LDS: top-K, or two Gaussians per thread, or one per thread with the weight_mod tile.
+template <bool FK>
+static int launch_lbs_forward(LbsArgs& a, void* bone_table, hipStream_t s) {
+  const int N = a.N, J = a.J;
+  if (J > MAX_J) {  // (the bone table is a <= 64-joint form)
+    ProfScope ps(PROF_LBS_FWD, s);
+    if (a.K > 0) hipLaunchKernelGGL((lbs_forward_kernel<true, false, 1, MAX_J_WIDE>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((lbs_forward_kernel<false, false, 1, MAX_J_WIDE>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a);
+  } else if (lbs_use_scalar(a, bone_table) && !a.nn_weight && !a.nn_idx) {
+    Bone* table = (Bone*)bone_table;
+    if constexpr (FK) hipLaunchKernelGGL(lbs_fk_table_kernel, dim3(1), dim3(64), 0, s, a, table);
+    else hipLaunchKernelGGL(lbs_bone_table_kernel, dim3(1), dim3(64), 0, s, a, table);
+    ProfScope ps(PROF_LBS_FWD, s);
+    if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_scalar_kernel<2>), dim3(lbs_grid(N, 2)), dim3(256), 0, s, a, table);
+    else hipLaunchKernelGGL((lbs_forward_scalar_kernel<1>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a, table);
+  } else {
+    ProfScope ps(PROF_LBS_FWD, s);
+    if (a.K > 0) hipLaunchKernelGGL((lbs_forward_kernel<true, FK, 1>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a);
+    else if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_kernel<false, FK, 2>), dim3(lbs_grid(N, 2)), dim3(256), 0, s, a);
+    else { const size_t lds = lbs_mod_lds(a, 1); hipLaunchKernelGGL((lbs_forward_kernel<false, FK, 1>), dim3(lbs_grid(N, 1)), dim3(256), lds, s, a); }
+  }
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 int riggs_fk_forward(int32_t J, const float* local_rot, const float* joints, const int32_t* parents,
@@ -1198,37 +1252,6 @@ int riggs_fk_backward(int32_t J, const float* local_rot, const float* joints, co
   return 0;
 }
 
-static int fill_lbs(LbsArgs& a, int32_t N, int32_t J, int32_t K, const float* x, const float* joints,
-                    const int32_t* parents, const float* rho, const float* transforms, const float* node_rot,
-                    const float* gt, const float* mask) {
-  RIGGS_REQUIRE(J >= 2 && J <= MAX_J_WIDE, "num_joints must be in [2, 256]");
-  RIGGS_REQUIRE(N >= 0, "num_points < 0");
-  RIGGS_REQUIRE(K < J, "K must be < num_joints");
-  memset(&a, 0, sizeof(a));
-  a.N = N; a.J = J; a.K = K; a.x = x; a.joints = joints; a.parents = parents; a.node_radius_log = rho;
-  a.transforms = transforms; a.node_rot = node_rot; a.global_trans = gt; a.motion_mask = mask;
-  return 0;
-}
-
-// two Gaussians per thread in the all-bones forward (see lbs_forward_kernel) where the launch still fills the chip
-static bool lbs_two_per_thread(int N, int J) { return N >= LBS_PTS2_MIN_N && J >= LBS_PTS2_MIN_J; }
-
-static unsigned lbs_grid(int N, int pts) { return (unsigned)((N + 256 * pts - 1) / (256 * pts)); }
-// The bone records through the scalar cache (lbs_forward_scalar_kernel) where that wins: the large, many-joint scenes whose loop is
-// bound by the LDS handing every wave the records (2 M x 64: 129 -> 104 us; at 300 k x 24 the extra one-workgroup launch in front
-// costs what the loop gains: 13.0 against 15.9 us — tools/lbs_scalar_ab.py); the caller must have handed over a table
-// (riggs_lbs_bone_table_bytes).  riggs_set_option("lbs_scalar", 1) forces it at every size (the A/B), -1 forbids it.
-static bool lbs_use_scalar(const LbsArgs& a, const void* bone_table) {
-  if (!bone_table || a.K > 0 || a.weight_mod) return false;
-  const int o = option(OPT_LBS_SCALAR);
-  return o > 0 || (o == 0 && lbs_two_per_thread(a.N, a.J));
-}
-// the forward's weight_mod tile (one Gaussian per thread, up to 47 bones: 48 KB; beyond, the rows are read from global memory)
-static size_t lbs_mod_lds(LbsArgs& a, int pts) {
-  a.mod_lds = (a.weight_mod && pts == 1 && a.J - 1 <= 47) ? 1 : 0;
-  return a.mod_lds ? (size_t)256 * ((a.J - 1) | 1) * sizeof(float) : 0;
-}
-
 int riggs_lbs_forward(int32_t N, int32_t J, int32_t K, const float* x, const float* joints, const int32_t* parents,
                       const float* node_radius_log, const float* transforms, const float* node_rot,
                       const float* global_trans, const float* motion_mask, const float* weight_mod, float* d_xyz,
@@ -1240,32 +1263,7 @@ int riggs_lbs_forward(int32_t N, int32_t J, int32_t K, const float* x, const flo
   a.weight_mod = weight_mod;
   RIGGS_REQUIRE(weight_mod == nullptr || K <= 0, "weight_mod is supported with K = -1 (all bones) only");
   if (N == 0) return 0;
-  if (J > MAX_J) {  // (the bone table is a <= 64-joint form)
-    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-    if (a.K > 0) hipLaunchKernelGGL(lbs_forward_wide_kernel<true>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(lbs_forward_wide_kernel<false>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    RIGGS_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (lbs_use_scalar(a, bone_table) && !nn_weight && !nn_idx) {
-    Bone* table = (Bone*)bone_table;
-    hipLaunchKernelGGL(lbs_bone_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, table);
-    {
-      ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-      if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_scalar_kernel<2>), dim3(lbs_grid(N, 2)), dim3(256), 0, (hipStream_t)stream, a, table);
-      else hipLaunchKernelGGL((lbs_forward_scalar_kernel<1>), dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a, table);
-    }
-    RIGGS_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  {
-    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-    if (a.K > 0) hipLaunchKernelGGL((lbs_forward_kernel<true, false, 1>), dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    else if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_kernel<false, false, 2>), dim3(lbs_grid(N, 2)), dim3(256), 0, (hipStream_t)stream, a);
-    else { const size_t lds = lbs_mod_lds(a, 1); hipLaunchKernelGGL((lbs_forward_kernel<false, false, 1>), dim3(lbs_grid(N, 1)), dim3(256), lds, (hipStream_t)stream, a); }
-  }
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_lbs_forward<false>(a, bone_table, (hipStream_t)stream);
 }
 
 int riggs_lbs_forward_fk(int32_t N, int32_t J, int32_t K, const float* x, const float* joints, const int32_t* parents,
@@ -1286,31 +1284,8 @@ int riggs_lbs_forward_fk(int32_t N, int32_t J, int32_t K, const float* x, const 
     // whole sweep (one barrier per level: a 256-joint chain is 255 levels)
     rc = riggs_fk_forward(J, local_rot, joints, parents, global_trans, transforms, node_rot, d_nodes, stream);
     if (rc) return rc;
-    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-    if (a.K > 0) hipLaunchKernelGGL(lbs_forward_wide_kernel<true>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(lbs_forward_wide_kernel<false>, dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    RIGGS_HIP_CHECK(hipGetLastError());
-    return 0;
   }
-  if (lbs_use_scalar(a, bone_table)) {
-    Bone* table = (Bone*)bone_table;
-    hipLaunchKernelGGL(lbs_fk_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, table);
-    {
-      ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-      if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_scalar_kernel<2>), dim3(lbs_grid(N, 2)), dim3(256), 0, (hipStream_t)stream, a, table);
-      else hipLaunchKernelGGL((lbs_forward_scalar_kernel<1>), dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a, table);
-    }
-    RIGGS_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  {
-    ProfScope ps(PROF_LBS_FWD, (hipStream_t)stream);
-    if (a.K > 0) hipLaunchKernelGGL((lbs_forward_kernel<true, true, 1>), dim3(lbs_grid(N, 1)), dim3(256), 0, (hipStream_t)stream, a);
-    else if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_kernel<false, true, 2>), dim3(lbs_grid(N, 2)), dim3(256), 0, (hipStream_t)stream, a);
-    else { const size_t lds = lbs_mod_lds(a, 1); hipLaunchKernelGGL((lbs_forward_kernel<false, true, 1>), dim3(lbs_grid(N, 1)), dim3(256), lds, (hipStream_t)stream, a); }
-  }
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_lbs_forward<true>(a, bone_table, (hipStream_t)stream);
 }
 
 size_t riggs_lbs_bone_table_bytes(void) { return sizeof(Bone) * MAX_J; }

@@ -52,7 +52,7 @@ struct FkLane {
 };
 __device__ __forceinline__ float fk_lane_get(float v, int src) { return __shfl(v, src); }
 
-// what a lane reads from memory for its joint (a caller with other loads to issue fetches these first: fk_load)
+// what a lane reads from memory for its joint (a caller with other loads to issue fetches these first: fk_load_joint)
 struct FkIn {
   float q[4];      // local rotation (un-normalised wxyz)
   float c[3];      // the PARENT joint's rest position
@@ -62,10 +62,10 @@ struct FkIn {
   float G[12];     // (backward, optional) the joint's global transform as the forward left it: the chain is then not re-run
   int par;
 };
-__device__ __forceinline__ void fk_load(int J, const float* __restrict__ local_rot, const float* __restrict__ joints,
-                                        const int32_t* __restrict__ parents, const float* __restrict__ dL_dG_in,
-                                        const float* __restrict__ dL_dnodes, FkIn& in, const float* __restrict__ transforms = nullptr) {
-  const int j = threadIdx.x & 63;
+// joint j = the thread (fk_block_*), or the lane (fk_load)
+__device__ __forceinline__ void fk_load_joint(int j, int J, const float* __restrict__ local_rot, const float* __restrict__ joints,
+                                              const int32_t* __restrict__ parents, const float* __restrict__ dL_dG_in,
+                                              const float* __restrict__ dL_dnodes, FkIn& in, const float* __restrict__ transforms = nullptr) {
   in.par = 0;
 #pragma unroll
   for (int e = 0; e < 4; e++) in.q[e] = (e == 0) ? 1.f : 0.f;
@@ -94,6 +94,74 @@ __device__ __forceinline__ void fk_load(int J, const float* __restrict__ local_r
     }
   }
 }
+__device__ __forceinline__ void fk_load(int J, const float* __restrict__ local_rot, const float* __restrict__ joints,
+                                        const int32_t* __restrict__ parents, const float* __restrict__ dL_dG_in,
+                                        const float* __restrict__ dL_dnodes, FkIn& in, const float* __restrict__ transforms = nullptr) {
+  fk_load_joint(threadIdx.x & 63, J, local_rot, joints, parents, dL_dG_in, dL_dnodes, in, transforms);
+}
+
+// T_j = [R | c - R c]: the joint's rotation about its PARENT joint (skeleton_warp.py:249-258)
+__device__ __forceinline__ void fk_local_T(const FkIn& in, float (&T)[12]) {
+  float q[4] = {in.q[0], in.q[1], in.q[2], in.q[3]};
+  float R[9];
+  quat_to_R_unnorm(q, R);
+  const float cx = in.c[0], cy = in.c[1], cz = in.c[2];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2];
+    const float c = (r == 0) ? cx : (r == 1 ? cy : cz);
+    T[4 * r + 3] = c - (R[3 * r] * cx + R[3 * r + 1] * cy + R[3 * r + 2] * cz);  // rotate about the PARENT joint
+  }
+}
+
+// (backward) the seed of the reverse sweep: dG = dL/dtransforms + dL/dd_nodes (x) [x; 1]  (posed_j = G_j [joint_j; 1]); zeros off the chain
+__device__ __forceinline__ void fk_seed_dG(bool on, const FkIn& in, float (&dG)[12]) {
+#pragma unroll
+  for (int e = 0; e < 12; e++) dG[e] = 0.f;
+  if (on) {
+    const float x = in.x[0], y = in.x[1], z = in.x[2];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const float e = in.gn[r];  // posed_j = G_j [joint_j; 1]
+      dG[4 * r] = in.dG[4 * r] + e * x;
+      dG[4 * r + 1] = in.dG[4 * r + 1] + e * y;
+      dG[4 * r + 2] = in.dG[4 * r + 2] + e * z;
+      dG[4 * r + 3] = in.dG[4 * r + 3] + e;
+    }
+  }
+}
+
+// dT_j (dL/d of the joint's local transform) -> dq = dL/dlocal_rot through t = c - R c and quaternion_to_matrix
+__device__ __forceinline__ void fk_dq_from_dT(bool on, const FkIn& in, const float (&dT)[12], float (&dq)[4]) {
+  dq[0] = 0.f; dq[1] = 0.f; dq[2] = 0.f; dq[3] = 0.f;
+  if (on) {
+    const float cc[3] = {in.c[0], in.c[1], in.c[2]};
+    float dR[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) dR[3 * a + b] = dT[4 * a + b] - dT[4 * a + 3] * cc[b];  // t = c - R c
+    const float qr = in.q[0], qi = in.q[1], qj = in.q[2], qk = in.q[3];
+    const float n = qr * qr + qi * qi + qj * qj + qk * qk;
+    const float s = 2.0f / n;
+    // A = (R - I)/s
+    const float A[9] = {-(qj * qj + qk * qk), qi * qj - qk * qr, qi * qk + qj * qr,
+                        qi * qj + qk * qr, -(qi * qi + qk * qk), qj * qk - qi * qr,
+                        qi * qk - qj * qr, qj * qk + qi * qr, -(qi * qi + qj * qj)};
+    float dotA = 0.f;
+#pragma unroll
+    for (int e = 0; e < 9; e++) dotA += dR[e] * A[e];
+    const float gr = -qk * dR[1] + qj * dR[2] + qk * dR[3] - qi * dR[5] - qj * dR[6] + qi * dR[7];
+    const float gi = qj * dR[1] + qk * dR[2] + qj * dR[3] - 2.f * qi * dR[4] - qr * dR[5] + qk * dR[6] + qr * dR[7] - 2.f * qi * dR[8];
+    const float gj = -2.f * qj * dR[0] + qi * dR[1] + qr * dR[2] + qi * dR[3] + qk * dR[5] - qr * dR[6] + qk * dR[7] - 2.f * qj * dR[8];
+    const float gk = -2.f * qk * dR[0] - qr * dR[1] + qi * dR[2] + qr * dR[3] - 2.f * qk * dR[4] + qj * dR[5] + qi * dR[6] + qj * dR[7];
+    const float s2 = s * s;
+    dq[0] = s * gr - s2 * qr * dotA;
+    dq[1] = s * gi - s2 * qi * dotA;
+    dq[2] = s * gj - s2 * qj * dotA;
+    dq[3] = s * gk - s2 * qk * dotA;
+  }
+}
 
 __device__ __forceinline__ void fk_wave_forward(int J, const FkIn& in, FkLane& f, bool have_G = false) {
   const int j = threadIdx.x & 63;
@@ -102,18 +170,8 @@ __device__ __forceinline__ void fk_wave_forward(int J, const FkIn& in, FkLane& f
 #pragma unroll
   for (int e = 0; e < 12; e++) { f.T[e] = 0.f; f.G[e] = 0.f; }
   if (on) {
-    float q[4] = {in.q[0], in.q[1], in.q[2], in.q[3]};
-    float R[9];
-    quat_to_R_unnorm(q, R);
-    const int vp = in.par;
-    f.par = vp;
-    const float cx = in.c[0], cy = in.c[1], cz = in.c[2];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      f.T[4 * r] = R[3 * r]; f.T[4 * r + 1] = R[3 * r + 1]; f.T[4 * r + 2] = R[3 * r + 2];
-      const float c = (r == 0) ? cx : (r == 1 ? cy : cz);
-      f.T[4 * r + 3] = c - (R[3 * r] * cx + R[3 * r + 1] * cy + R[3 * r + 2] * cz);  // rotate about the PARENT joint
-    }
+    f.par = in.par;
+    fk_local_T(in, f.T);
   }
   // depth of every joint by pointer doubling (parents[i] < i: joint 0 is the root), the deepest level, the children
   int d = (on && j >= 1) ? 1 : 0, anc = f.par;
@@ -154,19 +212,7 @@ __device__ __forceinline__ void fk_wave_backward(int J, const FkIn& in, const Fk
   const int j = threadIdx.x & 63;
   const bool on = j < J;
   float dG[12];
-#pragma unroll
-  for (int e = 0; e < 12; e++) dG[e] = 0.f;
-  if (on) {
-    const float x = in.x[0], y = in.x[1], z = in.x[2];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const float e = in.gn[r];  // posed_j = G_j [joint_j; 1]
-      dG[4 * r] = in.dG[4 * r] + e * x;
-      dG[4 * r + 1] = in.dG[4 * r + 1] + e * y;
-      dG[4 * r + 2] = in.dG[4 * r + 2] + e * z;
-      dG[4 * r + 3] = in.dG[4 * r + 3] + e;
-    }
-  }
+  fk_seed_dG(on, in, dG);
   // deepest level first: the joints of level l + 1 (their dG is final) hand  [dR_G R_T^T + dt_G t_T^T | dt_G]  to their parents
   for (int l = f.maxlev - 1; l >= 0; l--) {
     float add[12];
@@ -190,6 +236,7 @@ __device__ __forceinline__ void fk_wave_backward(int J, const FkIn& in, const Fk
     }
   }
   // dT_j = Rp^T dG_j (both the rotation block and the translation column); the root's is its dG
+  // (written out in both forms: as a shared helper it reschedules the block form, fk_backward_wide_kernel)
   float dT[12];
   {
     float Gp[12];
@@ -201,84 +248,7 @@ __device__ __forceinline__ void fk_wave_backward(int J, const FkIn& in, const Fk
       for (int c = 0; c < 4; c++)
         dT[4 * r + c] = (j == 0) ? dG[4 * r + c] : Gp[r] * dG[c] + Gp[4 + r] * dG[4 + c] + Gp[8 + r] * dG[8 + c];
   }
-  dq[0] = 0.f; dq[1] = 0.f; dq[2] = 0.f; dq[3] = 0.f;
-  if (on) {
-    const float cc[3] = {in.c[0], in.c[1], in.c[2]};
-    float dR[9];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) dR[3 * a + b] = dT[4 * a + b] - dT[4 * a + 3] * cc[b];  // t = c - R c
-    const float qr = in.q[0], qi = in.q[1], qj = in.q[2], qk = in.q[3];
-    const float n = qr * qr + qi * qi + qj * qj + qk * qk;
-    const float s = 2.0f / n;
-    // A = (R - I)/s
-    const float A[9] = {-(qj * qj + qk * qk), qi * qj - qk * qr, qi * qk + qj * qr,
-                        qi * qj + qk * qr, -(qi * qi + qk * qk), qj * qk - qi * qr,
-                        qi * qk - qj * qr, qj * qk + qi * qr, -(qi * qi + qj * qj)};
-    float dotA = 0.f;
-#pragma unroll
-    for (int e = 0; e < 9; e++) dotA += dR[e] * A[e];
-    const float gr = -qk * dR[1] + qj * dR[2] + qk * dR[3] - qi * dR[5] - qj * dR[6] + qi * dR[7];
-    const float gi = qj * dR[1] + qk * dR[2] + qj * dR[3] - 2.f * qi * dR[4] - qr * dR[5] + qk * dR[6] + qr * dR[7] - 2.f * qi * dR[8];
-    const float gj = -2.f * qj * dR[0] + qi * dR[1] + qr * dR[2] + qi * dR[3] + qk * dR[5] - qr * dR[6] + qk * dR[7] - 2.f * qj * dR[8];
-    const float gk = -2.f * qk * dR[0] - qr * dR[1] + qi * dR[2] + qr * dR[3] - 2.f * qk * dR[4] + qj * dR[5] + qi * dR[6] + qj * dR[7];
-    const float s2 = s * s;
-    dq[0] = s * gr - s2 * qr * dotA;
-    dq[1] = s * gi - s2 * qi * dotA;
-    dq[2] = s * gj - s2 * qj * dotA;
-    dq[3] = s * gk - s2 * qk * dotA;
-  }
-}
-
-// fk_load for joint j = the thread (fk_block_*)
-__device__ __forceinline__ void fk_load_joint(int j, int J, const float* __restrict__ local_rot, const float* __restrict__ joints,
-                                              const int32_t* __restrict__ parents, const float* __restrict__ dL_dG_in,
-                                              const float* __restrict__ dL_dnodes, FkIn& in, const float* __restrict__ transforms) {
-  in.par = 0;
-#pragma unroll
-  for (int e = 0; e < 4; e++) in.q[e] = (e == 0) ? 1.f : 0.f;
-#pragma unroll
-  for (int e = 0; e < 3; e++) { in.c[e] = 0.f; in.x[e] = 0.f; in.gn[e] = 0.f; }
-#pragma unroll
-  for (int e = 0; e < 12; e++) { in.dG[e] = 0.f; in.G[e] = 0.f; }
-  if (j < J) {
-    if (transforms) {
-#pragma unroll
-      for (int e = 0; e < 12; e++) in.G[e] = transforms[12 * j + e];
-    }
-    const int vp = (j == 0) ? 0 : parents[j];  // skeleton_warp.py:246-247
-    in.par = vp;
-#pragma unroll
-    for (int e = 0; e < 4; e++) in.q[e] = local_rot[4 * j + e];
-#pragma unroll
-    for (int e = 0; e < 3; e++) { in.x[e] = joints[3 * j + e]; in.c[e] = joints[3 * vp + e]; }
-    if (dL_dG_in) {
-#pragma unroll
-      for (int e = 0; e < 12; e++) in.dG[e] = dL_dG_in[12 * j + e];
-    }
-    if (dL_dnodes) {
-#pragma unroll
-      for (int e = 0; e < 3; e++) in.gn[e] = dL_dnodes[3 * j + e];
-    }
-  }
-}
-// T_j = [R | c - R c]: the joint's rotation about its PARENT joint (skeleton_warp.py:249-258)
-__device__ __forceinline__ void fk_local_T(const FkIn& in, float (&T)[12]) {
-  float q[4] = {in.q[0], in.q[1], in.q[2], in.q[3]};
-  float R[9];
-  quat_to_R_unnorm(q, R);
-  const float cx = in.c[0], cy = in.c[1], cz = in.c[2];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2];
-    const float c = (r == 0) ? cx : (r == 1 ? cy : cz);
-    T[4 * r + 3] = c - (R[3 * r] * cx + R[3 * r + 1] * cy + R[3 * r + 2] * cz);  // rotate about the PARENT joint
-  }
-}
-
-// dT_j (dL/d of the joint's local transform) -> dq = dL/dlocal_rot through t = c - R c and quaternion_to_matrix
-__device__ __forceinline__ void fk_dq_from_dT(bool on, const FkIn& in, const float (&dT)[12], float (&dq)[4]) {
+  // (fk_dq_from_dT, written out: through the helper the compiler contracts one product of the PoseMLP backward differently)
   dq[0] = 0.f; dq[1] = 0.f; dq[2] = 0.f; dq[3] = 0.f;
   if (on) {
     const float cc[3] = {in.c[0], in.c[1], in.c[2]};
@@ -385,19 +355,7 @@ __device__ __forceinline__ void fk_block_backward(int J, const FkIn& in, const F
   const int j = threadIdx.x;
   const bool on = j < J;
   float dG[12];
-#pragma unroll
-  for (int e = 0; e < 12; e++) dG[e] = 0.f;
-  if (on) {
-    const float x = in.x[0], y = in.x[1], z = in.x[2];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const float e = in.gn[r];  // posed_j = G_j [joint_j; 1]
-      dG[4 * r] = in.dG[4 * r] + e * x;
-      dG[4 * r + 1] = in.dG[4 * r + 1] + e * y;
-      dG[4 * r + 2] = in.dG[4 * r + 2] + e * z;
-      dG[4 * r + 3] = in.dG[4 * r + 3] + e;
-    }
-  }
+  fk_seed_dG(on, in, dG);
   // deepest level first: the joints of level l + 1 (their dG is final) hand  [dR_G R_T^T + dt_G t_T^T | dt_G]  to their parents
   for (int l = f.maxlev - 1; l >= 0; l--) {
     if (on && f.lev == l + 1) {

@@ -457,31 +457,10 @@ struct PmFkArgs {
   float* fixed_loss_out;
 };
 
-// the one-launch-per-layer path's form of the same term (the fused kernel adds it while the chain's gradients sit in LDS)
+// the one-launch-per-layer path's form of the same term (the fused kernel adds it while the chain's gradients sit in LDS); beyond 64 joints
+// (4 J > 256 entries) a thread walks several
 __global__ __launch_bounds__(256) void pm_fixed_add_kernel(int J, const float* __restrict__ local_rot, const float* __restrict__ coef,
                                                            float* __restrict__ dq, float* __restrict__ loss_out) {
-  __shared__ float s_p[4];
-  const int t = threadIdx.x;
-  float d = 0.f;
-  if (t < 4 * J) {
-    d = local_rot[t] - ((t & 3) == 0 ? 1.f : 0.f);
-    if (coef) dq[t] += coef[0] * d;
-  }
-  float ss = d * d;
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-  if ((t & 63) == 0) s_p[t >> 6] = ss;
-  __syncthreads();
-  if (t == 0 && loss_out) loss_out[0] = ((s_p[0] + s_p[1]) + (s_p[2] + s_p[3])) / (float)(4 * J);
-}
-// dst += src over n floats (the layered backward_fk: the heads' extra rotation gradient onto the chain's)
-__global__ __launch_bounds__(256) void pm_add_kernel(int n, const float* __restrict__ src, float* __restrict__ dst) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] += src[i];
-}
-
-// ... for more than 64 joints (4 J > 256 entries: a thread walks several)
-__global__ __launch_bounds__(256) void pm_fixed_add_wide_kernel(int J, const float* __restrict__ local_rot, const float* __restrict__ coef,
-                                                                float* __restrict__ dq, float* __restrict__ loss_out) {
   __shared__ float s_p[4];
   float ss = 0.f;
   for (int t = threadIdx.x; t < 4 * J; t += 256) {
@@ -494,6 +473,12 @@ __global__ __launch_bounds__(256) void pm_fixed_add_wide_kernel(int J, const flo
   __syncthreads();
   if (threadIdx.x == 0 && loss_out) loss_out[0] = ((s_p[0] + s_p[1]) + (s_p[2] + s_p[3])) / (float)(4 * J);
 }
+// dst += src over n floats (the layered backward_fk: the heads' extra rotation gradient onto the chain's)
+__global__ __launch_bounds__(256) void pm_add_kernel(int n, const float* __restrict__ src, float* __restrict__ dst) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] += src[i];
+}
+
 #undef PM_FAULT_BIT
 #define PM_FAULT_BIT 2u
 __global__ __launch_bounds__(PMF_WAVES * 64) void pm_backward_fused_kernel(PoseMlpDesc d, PoseMlpGradDesc g, PmFkArgs fk,
@@ -851,8 +836,7 @@ static int pm_backward_impl(int32_t depth, int32_t width, int32_t multires, int3
       RIGGS_HIP_CHECK(hipGetLastError());
     }
     if (fk.fixed_coef || fk.fixed_loss_out) {
-      if (fk.J <= MAX_J) hipLaunchKernelGGL(pm_fixed_add_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
-      else hipLaunchKernelGGL(pm_fixed_add_wide_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
+      hipLaunchKernelGGL(pm_fixed_add_kernel, dim3(1), dim3(256), 0, s, fk.J, fk.local_rot, fk.fixed_coef, fk.dq_out, fk.fixed_loss_out);
       RIGGS_HIP_CHECK(hipGetLastError());
     }
     g_rotation = fk.dq_out; g_translation = fk.dgt_out;

@@ -157,12 +157,13 @@ def test_deform_forward_values_vs_oracle_at_both_sides_of_the_two_per_lane_switc
         U.assert_close(dx[256:512], ox[256:512], "d_xyz second half of the first 512-block (%s)" % tag, 2e-5)
 
 
-@pytest.mark.parametrize("N,J", [(1, 2), (257, 8), (40_003, 24), (70_001, 64)])
+@pytest.mark.parametrize("N,J", [(1, 2), (257, 8), (40_003, 24), (70_001, 64), (1_000_001, 16)])
 def test_scalar_bone_records_give_the_same_bits_as_the_lds_form(N, J):
     """riggs_set_option("lbs_scalar", 1): the all-bones skinning forward with the bone records read through the scalar cache (a
     one-workgroup table launch in front — with the kinematic chain inside it in the _fk entry) — against the LDS form
     ("lbs_scalar" -1): identical bits in d_xyz / d_rotation / d_nodes and the chain's outputs, through both entry points; the default
-    (0) picks by size and is what the million-Gaussian tests above run."""
+    (0) picks by size and is what the million-Gaussian tests above run.  (1 000 001 x 16: two Gaussians per lane — the only launch
+    of the LDS form's PTS = 2 instantiations in the suite, the default taking the scalar form from that size on.)"""
     from riggs_amd import _lib as L
     sc = synth.make_scene(N, J, 5 + J)
     mask = torch.rand(N, 1, generator=torch.Generator().manual_seed(N)).cuda()
@@ -181,6 +182,27 @@ def test_scalar_bone_records_give_the_same_bits_as_the_lds_form(N, J):
         L.set_option("lbs_scalar", 0)
     for a, b in zip(res[-1], res[1]):
         assert torch.equal(a, b)
+    # riggs_lbs_forward_fk itself with a bone table (lbs_fk_table_kernel + lbs_forward_scalar_kernel) against its LDS form: every
+    # output of the call, the chain's transforms / node_rot / d_nodes included, bit for bit
+    lib = L.lib()
+    jc, rc, qc, gtc = (sc[k].float().contiguous().cuda() for k in ("joints", "node_radius", "local_rotation", "global_trans"))
+    p32 = torch.as_tensor(sc["parents"]).to(torch.int32).cuda()
+    xc, mc = x.float().contiguous(), mask.contiguous()
+    table = torch.empty(int(lib.riggs_lbs_bone_table_bytes()), dtype=torch.uint8, device="cuda")
+    raw = {}
+    try:
+        for flag in (-1, 1):
+            L.set_option("lbs_scalar", flag)
+            tr, nr, dn, dx, dr = (torch.full(sh, float("nan"), device="cuda") for sh in ((J, 12), (J, 4), (J, 3), (N, 3), (N, 4)))
+            L.check(lib.riggs_lbs_forward_fk(N, J, -1, xc.data_ptr(), jc.data_ptr(), p32.data_ptr(), rc.data_ptr(), qc.data_ptr(),
+                                             gtc.data_ptr(), mc.data_ptr(), None, tr.data_ptr(), nr.data_ptr(), dn.data_ptr(),
+                                             dx.data_ptr(), dr.data_ptr(), table.data_ptr(), L.stream_ptr()), "riggs_lbs_forward_fk")
+            torch.cuda.synchronize()
+            raw[flag] = (tr, nr, dn, dx, dr)
+    finally:
+        L.set_option("lbs_scalar", 0)
+    for a, b in zip(raw[-1], raw[1]):
+        assert not torch.isnan(a).any() and torch.equal(a, b)
 
 
 @pytest.mark.parametrize("keep", [0.0, 0.05, 0.5])

@@ -1,6 +1,6 @@
 """-m gpu: the deformation kernels of 63..256-joint skeletons pinned per element to float64 (tests/skin_ref.py), through the C ABI
 so that every output and workspace is under the test's control.  Each kernel is checked from the fp32 inputs it read (the
-skinning from the chain kernel's own transforms), across the dispatch boundaries the wide kernels introduced: 64 / 65 joints,
+skinning from the chain kernel's own transforms), across the dispatch boundaries the 65-256-joint kernels introduced: 64 / 65 joints,
 bone passes of 64 and mask words of 32 bones, the bone-lane backward's 1024-Gaussian workgroups, K from 1 to J - 1.  Every
 output is a view into a larger buffer whose sentinel tail must survive bit for bit, and every per-Gaussian input carries a NaN
 tail past row N, so that a read past N poisons a result."""
@@ -220,7 +220,7 @@ def run_skin(c):
                                           nidx.data_ptr(), None, L.stream_ptr()), "riggs_lbs_forward")
             torch.cuda.synchronize()
             assert tail_intact(nib, N, -77)
-            if J > 64:  # the _fk form launches the same lbs_forward_wide_kernel after its chain: bit for bit
+            if J > 64:  # the _fk form launches the same 256-joint lbs_forward_kernel after its chain: bit for bit
                 assert torch.equal(dx, dx2) and torch.equal(dr, dr2), "riggs_lbs_forward_fk != riggs_lbs_forward " + tag
         sel = nidx.cpu() - 1
         # The kernel's bone_d2 is contracted into FMAs (see tests/skin_ref.py), so the numpy float32 restatement does not pick
@@ -245,7 +245,9 @@ def run_skin(c):
     torch.cuda.synchronize()
     for buf, rows in ((dGb, J), (drhob, J), (dgtb, 3), (dmb, N)) + (((dwb, N),) if dw is not None else ()):
         assert torch.isnan(buf[rows:]).all(), "write past the end " + tag
-    depth = R.depth_topk(N) if K > 0 else R.depth_bonelane(N, J)
+    # (the <= 64-joint bone-lane backward gives a workgroup 4096 / 8192 Gaussians from 4 / 8 x 240 x 1024 on: deform.hip)
+    gpb = 1024 if J > 64 or N < 4 * 240 * 1024 else (4096 if N < 8 * 240 * 1024 else 8192)
+    depth = R.depth_topk(N) if K > 0 else R.depth_bonelane(N, J, gpb)
     dev = "cuda"
     ref = R.skin(x.to(dev), joints.to(dev), parents.to(dev), rho.to(dev), tr, nr, gt.to(dev),
                  None if mask is None else mask.to(dev), None if wm is None else wm.to(dev),
@@ -288,6 +290,21 @@ def _grid():
               dict(J=256, N=300_000, K=-1, topo="broom", mask="zeros", cot="consistent", wm=True, fk=True, seed=2),
               dict(J=129, N=300_000, K=3, topo="tree", mask="ones", cot="consistent", wm=False, fk=False, seed=3),
               dict(J=193, N=300_000, K=33, topo="star", mask="none", cot="random", wm=False, fk=True, seed=4)]
+    # the top-K forward's nn_weight / nn_idx (ascending d2) on both sides of 64 joints — the register mask and the LDS column
+    # of the one selection code — at K = 3 and K = J - 1
+    for j, (J, K) in enumerate([(64, 3), (64, 63), (65, 3), (65, 64)]):
+        cases.append(dict(J=J, N=257, K=K, topo=topos[j % 5], mask=masks[j % 4], cot="random", wm=False, fk=False, seed=800 + j))
+    # the <= 64-joint bone-lane backward's large-scene workgroups (4096 and 8192 Gaussians: N >= 4 x 240 x 1024 and
+    # N >= 8 x 240 x 1024) with one block of bones, a sparse cotangent, with and without weight_mod
+    for j, N in enumerate([4 * 240 * 1024 + 1, 8 * 240 * 1024 + 1]):
+        for wm in (False, True):
+            cases.append(dict(J=9, N=N, K=-1, topo="tree", mask="rand", cot="sparse", wm=wm, fk=False, seed=900 + 2 * j + wm))
+    # ... and its 2 to 7 blocks of bones (J - 1 = 9, 17, 25, 33, 41, 49), each with weight_mod (41 bones and fewer: the
+    # forward stages weight_mod through its LDS tile) and without it (then with the chain inside the forward)
+    for j, J in enumerate([10, 18, 26, 34, 42, 50]):
+        for wm in (j % 2 == 0, j % 2 == 1):
+            cases.append(dict(J=J, N=1025, K=-1, topo=topos[j % 5], mask=masks[j % 4], cot=cots[j % 5], wm=wm, fk=not wm,
+                              seed=950 + j + (0 if wm == (j % 2 == 0) else 10)))
     return cases
 
 

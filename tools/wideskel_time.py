@@ -1,5 +1,6 @@
 """Times of the deformation path over skeleton sizes on both sides of the 64-joint switch (J <= 64: one-wave chain, LDS records
-of <= 63 bones; J > 64: the workgroup chain and the *_wide skinning kernels), trees and chains, N = 300 k:
+of <= 63 bones; J > 64: the workgroup chain, the 256-joint instantiation of the skinning forward and the bone-lane
+backward in passes of 64 bones), trees and chains, N = 300 k:
 FK forward / backward, the all-bones skinning forward / backward (incl. its finish kernel) — each from a graph of 20 launches,
 best of 5 replays — and the PoseMLP forward / backward (the network SkeletonWarp builds, eager calls, mean of 20).
 usage: python tools/wideskel_time.py [--out profiles/wideskel_times.json]"""
