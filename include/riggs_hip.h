@@ -980,6 +980,14 @@ int32_t riggs_fps_blocks(int32_t N);
 size_t riggs_fps_workspace_bytes(int32_t N);
 int riggs_fps_sample(int32_t N, int32_t npoint, const float* xyz, int64_t row_stride, const int64_t* start, void* workspace,
                      int64_t* out_indices, riggs_stream stream);
+/* The same sweep over rows of D fp32, 1 <= D <= 64 (the stage-1 node sampling over 16-sample trajectories: D = 48), row_stride
+ * floats apart (>= D).  Squared distance: the sequential fp32 sum ((t_0^2 + t_1^2) + t_2^2) + ... over ascending columns with
+ * t_k = fl(p_k - c_k), every product and sum rounded: at D = 3 the indices of riggs_fps_sample.  The rows are transposed once per
+ * call into a (D, N) image inside the workspace (riggs_fps_rows_workspace_bytes(N, D) bytes, 256-byte aligned: 4 N D bytes for the
+ * image on top of nearest and the partials), then one plain launch per picked point.  start, out_indices, npoint as above. */
+size_t riggs_fps_rows_workspace_bytes(int32_t N, int32_t D);
+int riggs_fps_sample_rows(int32_t N, int32_t D, int32_t npoint, const float* rows, int64_t row_stride, const int64_t* start,
+                          void* workspace, int64_t* out_indices, riggs_stream stream);
 
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);

@@ -279,10 +279,11 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
         return super().load_state_dict(state_dict, strict=False)
 
     def init(self, opt, init_pcl, hyper_pcl=None, keep_all=False, force_init=False, as_gs_force_with_motion_mask=False,
-             force_gs_keep_all=False, reset_bbox=True, **kwargs):
+             force_gs_keep_all=False, reset_bbox=True, *, start=None, **kwargs):
         """Nodes from the initial point cloud (time_utils.py:874-922): all of it (``keep_all``, or fewer points than nodes:
-        new parameters, the optimizer must be set up again) or a farthest-point sample (random start) of it or of
-        ``hyper_pcl``; radius log(0.1 scene range), weights 0; then the node Gaussians, set up for training with ``opt``."""
+        new parameters, the optimizer must be set up again) or a farthest-point sample of it or of ``hyper_pcl`` (from a random
+        start, or from index ``start`` for a run that can be repeated); radius log(0.1 scene range), weights 0; then the node
+        Gaussians, set up for training with ``opt``."""
         from .gaussian_model import farthest_point_sample
         if bool(self.inited) and not force_init:
             return
@@ -294,7 +295,8 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
             print("Initialization with all pcl. Need to reset the optimizer.")
         else:
             pcl_to_samp = init_pcl if hyper_pcl is None else hyper_pcl
-            init_nodes_idx = farthest_point_sample(pcl_to_samp.detach()[None], self.node_num)[0]
+            first = {} if start is None else {"start": torch.as_tensor(start, dtype=torch.long).reshape(1)}
+            init_nodes_idx = farthest_point_sample(pcl_to_samp.detach()[None], self.node_num, **first)[0]
             self.nodes.data = torch.cat([init_pcl[init_nodes_idx].float(), 1e-2 * torch.ones(self.node_num, self.hyper_dim, device=dev)], -1)
         scene_range = init_pcl.max() - init_pcl.min()
         if self.skinning:
@@ -318,6 +320,53 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
             self.as_gaussians.training_setup(opt)
         print(f"Control node initialized with {self.nodes.shape[0]} from {init_pcl.shape[0]} points.")
         return init_nodes_idx
+
+    @torch.no_grad()
+    def hyper_trajectories(self, x, motion_mask, time_num=16):
+        """(N, 3 time_num) rows the nodes are sampled by (train_gui.py:1349-1357): every point's position at ``time_num`` times
+        from 0 to 1, ``x + query_network(x, t_i)['d_xyz'] * motion_mask``, side by side.  One network call per time, as the
+        reference makes them (the node network picks its workgroup shape by the row count)."""
+        x = x.detach()
+        t_samp = torch.linspace(0, 1, time_num).to(x.device)
+        trans_samp = [self.query_network(x=x, t=t_samp[i:i + 1, None].expand_as(x[..., :1]))["d_xyz"] * motion_mask
+                      for i in range(time_num)]
+        return (torch.stack(trans_samp, dim=1) + x[:, None]).reshape(x.shape[0], -1)
+
+    def downsample(self, opt, strategy="samp_hyper", with_dynamic_mask=False, start=None, **kwargs):
+        """The step at ``iterations_node_sampling`` (train_gui.py:1334-1370): thin the node Gaussians to the control nodes.
+        ``'direct'``: every node Gaussian becomes a node and the new node Gaussians share the old ones' parameters.
+        ``'samp_hyper'``: ``node_num`` of them — all, or with ``with_dynamic_mask`` those whose motion mask exceeds 0.5 — are
+        picked by a farthest-point sample of their trajectories (``hyper_trajectories``; from index ``start`` of the masked
+        points, or a random one), the nodes are re-initialised from the picks, the new node Gaussians take the picked
+        parameters and are set up for training with ``opt``.  ``kwargs`` go to ``init``.  Returns the picked indices into the
+        masked points (``None`` for ``'direct'``).  Resetting the deformation model's optimizer and zeroing the gradients
+        (train_gui.py:1346, 1372-1373) stay with the caller."""
+        old = self.as_gaussians
+
+        def take(pick):  # the new node Gaussians' appearance from the old ones'
+            new = self.as_gaussians
+            for name in ["_features_dc", "_features_rest", "_scaling", "_opacity", "_rotation"] + (["feature"] if new.fea_dim > 0 else []):
+                setattr(new, name, nn.Parameter(pick(getattr(old, name))))
+            return new
+
+        if strategy == "direct":
+            self.init(opt=opt, init_pcl=old.get_xyz, keep_all=True, force_init=True, reset_bbox=False, **kwargs)
+            take(lambda p: p)
+            return None
+        if strategy != "samp_hyper":
+            raise L.RiggsHipError("downsample: strategy is 'direct' or 'samp_hyper', got %r" % (strategy,))
+        xyz = old.get_xyz
+        hyper_pcl = self.hyper_trajectories(xyz, old.motion_mask)
+        dynamic_mask = old.motion_mask[..., 0] > .5
+        if not with_dynamic_mask:
+            dynamic_mask = torch.ones_like(dynamic_mask)
+        masked = int(dynamic_mask.sum()) if with_dynamic_mask else xyz.shape[0]
+        if masked < self.node_num:
+            raise L.RiggsHipError("downsample: %d points to sample %d nodes from" % (masked, self.node_num))
+        idx = self.init(init_pcl=xyz[dynamic_mask], hyper_pcl=hyper_pcl[dynamic_mask], force_init=True, opt=opt, reset_bbox=False,
+                        start=start, **kwargs)
+        take(lambda p: p[dynamic_mask][idx]).training_setup(opt)
+        return idx
 
     def cal_nn_weight(self, x, K=None, feature=None, nodes=None, gs_kernel=True, temperature=1.):
         """(time_utils.py:934-964) the K nearest nodes of every row of ``x`` in (xyz, hyper) space and their weights.  Used by

@@ -71,17 +71,21 @@ def strip_symmetric(m):  # upper triangle xx xy xz yy yz zz: utils/general_utils
 
 def farthest_point_sample(xyz, npoint, start=None):
     """(B, N, C) -> (B, npoint) indices of an iterative farthest-point sweep from a random start
-    (utils/time_utils.py:461-482); ``start`` (B,) fixes the first index.  One fp32 cloud of 3-vectors on the device goes to
-    the kernel (riggs_amd/fps.py: one launch per point); every other input keeps the torch loop."""
+    (utils/time_utils.py:461-482); ``start`` (B,) fixes the first index.  One fp32 cloud on the device goes to the kernels
+    (riggs_amd/fps.py: one launch per point) — 3-vectors to the 3-column one, rows of 1 to 64 floats (the trajectories the
+    stage-1 nodes are sampled by) to the wide one; every other input keeps the torch loop."""
     B, N, C = xyz.shape
-    if xyz.is_cuda and xyz.dtype is torch.float32 and B == 1 and C == 3 and N >= 1:
-        from .fps import farthest_point_sample as fps_hip
-        return fps_hip(xyz, npoint, start=start)
+    if xyz.is_cuda and xyz.dtype is torch.float32 and B == 1 and N >= 1:
+        from . import fps
+        if C == 3:
+            return fps.farthest_point_sample(xyz, npoint, start=start)
+        if 1 <= C <= fps.MAX_WIDTH:
+            return fps.farthest_point_sample_rows(xyz, npoint, start=start)
     return farthest_point_sample_torch(xyz, npoint, start)
 
 
 def farthest_point_sample_torch(xyz, npoint, start=None):
-    """The sweep as torch ops, about eight launches per point: CPU tensors, batches, C != 3, other dtypes."""
+    """The sweep as torch ops, about eight launches per point: CPU tensors, batches, C > 64, other dtypes."""
     B, N, _ = xyz.shape
     dev = xyz.device
     picked = torch.zeros(B, npoint, dtype=torch.long, device=dev)
