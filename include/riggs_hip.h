@@ -308,6 +308,35 @@ int riggs_lbs_backward(int32_t num_points, int32_t num_joints, int32_t K, const 
                        void* workspace /* riggs_lbs_backward_workspace_bytes(N, J) */, riggs_stream stream);
 size_t riggs_lbs_backward_workspace_bytes(int32_t num_points, int32_t num_joints);
 
+/* ---- Playback of a pose track (inference only: no backward exists; riggs_amd/playback.py).  Added symbols: riggs_version() is
+ * what it was.
+ * riggs_lbs_sequence_forward: M poses over ONE canonical cloud.  A launch in front runs the kinematic chain of every frame
+ * (one wave per frame up to 64 joints, one 256-thread workgroup beyond) and writes transforms (M,J,12), node_rot (M,J,4),
+ * d_nodes (M,J,3); the skinning launch keeps one Gaussian per thread — position, top-K set, weight_mod row: once — and walks
+ * the track in passes of riggs_lbs_sequence_pass_frames(J, K) frames whose (G, q) records lie in LDS, a bone's weight evaluated
+ * once per pass.  local_rot (M,J,4); global_trans (M,3) with global_trans_stride = 3, or (3,) with 0; motion_mask (N,) or NULL;
+ * weight_mod (N,J-1) or NULL (K = -1 only).  Outputs d_xyz (M,N,3), d_rotation (M,N,4): frame-major, a frame is contiguous.
+ * Same weights as riggs_lbs_forward (shared code), 2 <= J <= 256. */
+int riggs_lbs_sequence_forward(int32_t num_points, int32_t num_frames, int32_t num_joints, int32_t K, const float* x,
+                               const float* joints, const int32_t* parents, const float* node_radius_log, const float* local_rot,
+                               const float* global_trans, int32_t global_trans_stride, const float* motion_mask,
+                               const float* weight_mod, float* transforms, float* node_rot, float* d_nodes, float* d_xyz,
+                               float* d_rotation, riggs_stream stream);
+int32_t riggs_lbs_sequence_pass_frames(int32_t num_joints, int32_t K);
+/* The skinning weights of riggs_lbs_forward folded into one colour per Gaussian, without nn_weight / nn_idx in memory
+ * (skeleton_utils/visualization.py:118-129).  node_colors (J,3): bone k carries the colour of its child joint k + 1.
+ * mode 0: sum_k w_k colour; mode 1: the colour of the largest weight (the first such bone on equality), copied unchanged. */
+int riggs_skinning_colors(int32_t num_points, int32_t num_joints, int32_t K, const float* x, const float* joints,
+                          const int32_t* parents, const float* node_radius_log, const float* weight_mod /* or NULL */,
+                          const float* node_colors, int32_t mode, float* colors /* (N,3) */, riggs_stream stream);
+/* slerp_batch / run_interpolation (skeleton_utils/interpolation_utils.py:4-86) in one launch: for segment s < num_segments,
+ * frame f < num_frames and quaternion j < num_quats, out_rot[s * out_stride_segment + f * out_stride_frame + j * out_stride_quat
+ * .. + 4] = slerp(q0[s * q_stride + 4 j ..], q1[s * q_stride + 4 j ..], t[f]) (inputs need not be unit; strides in floats), and —
+ * unless trans0 is NULL — out_trans[(s * num_frames + f) * 3 ..] = (1 - t[f]) trans0[3 s ..] + t[f] trans1[3 s ..]. */
+int riggs_pose_slerp(int32_t num_segments, int32_t num_frames, int32_t num_quats, const float* q0, const float* q1,
+                     int64_t q_stride, const float* t, const float* trans0, const float* trans1, int64_t out_stride_segment,
+                     int64_t out_stride_frame, int64_t out_stride_quat, float* out_rot, float* out_trans, riggs_stream stream);
+
 /* =====================================================================
  * PoseMLP (time -> J quaternions + root translation), batch of ONE row:
  *   PoseMLP.forward   skeleton_utils/network_utils.py:134-150  (8 x Linear(256) + ReLU, the

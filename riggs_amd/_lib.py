@@ -178,6 +178,10 @@ _SIGS = {
     "riggs_lbs_forward_fk": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_P] * 15),
     "riggs_lbs_bone_table_bytes": (C.c_size_t, []),
     "riggs_lbs_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "riggs_lbs_sequence_forward": (C.c_int, [C.c_int32] * 4 + [_P] * 6 + [C.c_int32] + [_P] * 8),
+    "riggs_lbs_sequence_pass_frames": (C.c_int32, [C.c_int32, C.c_int32]),
+    "riggs_skinning_colors": (C.c_int, [C.c_int32] * 3 + [_P] * 6 + [C.c_int32, _P, _P]),
+    "riggs_pose_slerp": (C.c_int, [C.c_int32] * 3 + [_P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "riggs_pose_mlp_acts_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "riggs_pose_mlp_backward_workspace_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "riggs_pose_mlp_forward": (C.c_int, [C.c_int32] * 5 + [_P] * 13),

@@ -38,6 +38,7 @@ SOURCES = {
     "node_mlp.hip": ["-ffp-contract=off"],
     "flow.hip": ["-ffp-contract=off"],  # (the loss forms fl(w c) - fl(w m) as the reference does: no fused multiply-subtract)
     "fps.hip": ["-ffp-contract=off"],  # (the squared distance is fl(fl(dx dx + dy dy) + dz dz), as torch.sum gives it on the CPU)
+    "playback.hip": ["-ffp-contract=off"],  # (slerp / lerp in the reference's own steps: one rounding per operation)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

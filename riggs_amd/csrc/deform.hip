@@ -10,6 +10,10 @@
 // kernel on the benchmark's path, or measured slower: NOTES.md "deform: one body per step".
 // Backward reduces over the N Gaussians inside the kernel: wave64 DPP sums -> LDS -> one atomic
 // per workgroup per output.
+//   playback (inference only, at the end of the file): fk_sequence_* / lbs_sequence_kernel skin a whole pose track over one cloud,
+//            skinning_colors_kernel folds the same weights into a colour per Gaussian.  Shared with the forward: Bone, bone_geometry,
+//            bone_d2 / bone_d2_fast, topk_select, fast_exp and the chain; restated for these kernels only: the chain's write-out,
+//            the weight_mod tile, the line that forms v_k (fk_write_out, stage_mod_tile, bone_weight).
 #include <type_traits>
 
 #include "fk_device.h"
@@ -99,21 +103,26 @@ struct LbsArgs {
 // (transforms / node_rot: global memory, or the LDS arrays of a kinematic chain that this workgroup ran itself)
 __device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones, const float* transforms, const float* node_rot);
 __device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones) { stage_bones(a, bones, a.transforms, a.node_rot); }
+// the part of bone k's record that no pose changes: the segment, its clamped squared length, 1 / (2 r^2)
+__device__ __forceinline__ void bone_geometry(const LbsArgs& a, int k, Bone& b) {
+  const int child = k + 1, par = a.parents[child];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    b.a[c] = a.joints[3 * par + c];
+    b.ba[c] = a.joints[3 * child + c] - b.a[c];
+  }
+  const float l2 = __fadd_rn(__fadd_rn(__fmul_rn(b.ba[0], b.ba[0]), __fmul_rn(b.ba[1], b.ba[1])), __fmul_rn(b.ba[2], b.ba[2]));
+  b.len2c = fmaxf(l2, 1e-6f);
+  b.rl2 = 1.0f / b.len2c;
+  b.pad_[0] = 0.f; b.pad_[1] = 0.f; b.pad_[2] = 0.f;
+  const float rad = expf(a.node_radius_log[child]);
+  b.inv2r2 = 1.0f / (2.0f * rad * rad);
+}
 __device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones, const float* transforms, const float* node_rot) {
   for (int k = threadIdx.x; k < a.J - 1; k += blockDim.x) {
-    const int child = k + 1, par = a.parents[child];
+    const int child = k + 1;
     Bone b;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      b.a[c] = a.joints[3 * par + c];
-      b.ba[c] = a.joints[3 * child + c] - b.a[c];
-    }
-    const float l2 = __fadd_rn(__fadd_rn(__fmul_rn(b.ba[0], b.ba[0]), __fmul_rn(b.ba[1], b.ba[1])), __fmul_rn(b.ba[2], b.ba[2]));
-    b.len2c = fmaxf(l2, 1e-6f);
-    b.rl2 = 1.0f / b.len2c;
-    b.pad_[0] = 0.f; b.pad_[1] = 0.f; b.pad_[2] = 0.f;
-    const float rad = expf(a.node_radius_log[child]);
-    b.inv2r2 = 1.0f / (2.0f * rad * rad);
+    bone_geometry(a, k, b);
 #pragma unroll
     for (int e = 0; e < 12; e++) b.G[e] = transforms[12 * child + e];
 #pragma unroll
@@ -1159,6 +1168,222 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_wide_kernel(LbsArgs
   if (threadIdx.x < 3) part[B * 13 + threadIdx.x] = s_gt[threadIdx.x];
 }
 
+// ==================================================================================== playback: a pose track, skin colours
+// Inference only (riggs_lbs_sequence_forward, riggs_skinning_colors).  What depends on the canonical cloud alone — a Gaussian's
+// position, its top-K selection set, its weight_mod row, the bones' segments and radii — is computed or staged ONCE; the M poses
+// of a track then differ in the bones' (G, q) records only.  The distances and the selection are the forward's own functions (Bone,
+// bone_geometry, bone_d2 / bone_d2_fast, topk_select, fast_exp).  Three pieces of lbs_forward_kernel / fk_forward_kernel are written
+// out again below as helpers that only the playback kernels call — fk_write_out, stage_mod_tile, bone_weight: the forward keeps
+// its own lines, because a shared form of such lines has changed the compiled code of kernels on the benchmark's path before
+// (the note at the top of this file); they must be kept in step by hand, and tests/test_gpu_playback.py compares the two paths.
+struct SeqArgs {
+  int M;             // frames of the track
+  int slice_frames;  // frames per blockIdx.y: a multiple of the pass F
+  int gt_stride;     // floats between two frames' global_trans: 3, or 0 (one translation for the whole track)
+};
+
+// what a chain kernel leaves for its joint (a restatement of fk_forward_kernel's write-out)
+__device__ __forceinline__ void fk_write_out(int j, const float (&G)[12], const FkIn& in, const float* __restrict__ gt,
+                                             float* __restrict__ transforms, float* __restrict__ node_rot, float* __restrict__ d_nodes) {
+  const float x = in.x[0], y = in.x[1], z = in.x[2];
+#pragma unroll
+  for (int e = 0; e < 12; e++) transforms[12 * j + e] = G[e];
+#pragma unroll
+  for (int r = 0; r < 3; r++) d_nodes[3 * j + r] = (G[4 * r] * x + G[4 * r + 1] * y + G[4 * r + 2] * z + G[4 * r + 3]) + gt[r];
+  float q[4];
+  R_to_quat(G, q);
+#pragma unroll
+  for (int e = 0; e < 4; e++) node_rot[4 * j + e] = q[e];
+}
+// the kinematic chain of every frame of a track: one wave per frame (<= 64 joints) ...
+__global__ __launch_bounds__(64) void fk_sequence_kernel(int J, int gt_stride, const float* __restrict__ local_rot,
+                                                         const float* __restrict__ joints, const int32_t* __restrict__ parents,
+                                                         const float* __restrict__ global_trans, float* __restrict__ transforms,
+                                                         float* __restrict__ node_rot, float* __restrict__ d_nodes) {
+  const size_t f = blockIdx.x;
+  FkIn in;
+  fk_load(J, local_rot + f * J * 4, joints, parents, nullptr, nullptr, in);
+  FkLane fl;
+  fk_wave_forward(J, in, fl);
+  const int j = threadIdx.x;
+  if (j < J) fk_write_out(j, fl.G, in, global_trans + f * gt_stride, transforms + f * J * 12, node_rot + f * J * 4, d_nodes + f * J * 3);
+}
+// ... or one 256-thread workgroup per frame (65..256 joints)
+__global__ __launch_bounds__(256) void fk_sequence_wide_kernel(int J, int gt_stride, const float* __restrict__ local_rot,
+                                                               const float* __restrict__ joints, const int32_t* __restrict__ parents,
+                                                               const float* __restrict__ global_trans, float* __restrict__ transforms,
+                                                               float* __restrict__ node_rot, float* __restrict__ d_nodes) {
+  __shared__ FkWideShared sh;
+  const size_t f = blockIdx.x;
+  const int j = threadIdx.x;
+  FkIn in;
+  fk_load_joint(j, J, local_rot + f * J * 4, joints, parents, nullptr, nullptr, in);
+  FkWide fw;
+  fk_block_forward(J, in, fw, sh);
+  if (j < J) {
+    float G[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) G[e] = sh.G[j][e];
+    fk_write_out(j, G, in, global_trans + f * gt_stride, transforms + f * J * 12, node_rot + f * J * 4, d_nodes + f * J * 3);
+  }
+}
+
+// the bones' pose-independent records (their G / q stay zero: the track's poses have records of their own)
+__device__ __forceinline__ void stage_bone_geometry(const LbsArgs& a, Bone* bones) {
+  for (int k = threadIdx.x; k < a.J - 1; k += blockDim.x) {
+    Bone b;
+    bone_geometry(a, k, b);
+#pragma unroll
+    for (int e = 0; e < 12; e++) b.G[e] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; e++) b.q[e] = 0.f;
+    bones[k] = b;
+  }
+  __syncthreads();
+}
+// a restatement of lbs_forward_kernel's weight_mod tile: the wave's 64 rows, one contiguous run, copied coalesced into a wave-private LDS tile of
+// odd row stride (a.mod_lds: the launch reserved 256 (B | 1) floats); nullptr: the rows are read from global memory
+__device__ __forceinline__ float* stage_mod_tile(const LbsArgs& a, float* s_mod_dyn, int& BP) {
+  if (!a.mod_lds) return nullptr;
+  const int Bm = a.J - 1, lane_ = threadIdx.x & 63;
+  BP = Bm | 1;
+  float* s_mod = s_mod_dyn + (threadIdx.x >> 6) * 64 * BP;
+  const int ng = blockIdx.x * 256 + (threadIdx.x & ~63);
+  const int n_el = max(0, min(64, a.N - ng)) * Bm;
+  const float* run = a.weight_mod + (size_t)ng * Bm;
+  const float invB = 1.0f / (float)Bm;
+  for (int e = lane_; e < n_el; e += 64) {
+    const int r = (int)(((float)e + 0.5f) * invB);
+    s_mod[r * BP + (e - r * Bm)] = run[e];
+  }
+  return s_mod;
+}
+// v_k = exp(-d2 / (2 r^2)) [* weight_mod] + 1e-7 of the thread's Gaussian and bone k (skeleton_warp.py:66-71): the forward's line, restated
+template <bool TOPK>
+__device__ __forceinline__ float bone_weight(const LbsArgs& a, const Bone& b, int k, int B, int row, const float* s_mod, int BP,
+                                             float px, float py, float pz) {
+  const float d2 = TOPK ? bone_d2(b, px, py, pz) : bone_d2_fast(b, px, py, pz);
+  float u = fast_exp(-d2 * b.inv2r2);
+  if (a.weight_mod) u *= s_mod ? s_mod[(threadIdx.x & 63) * BP + k] : a.weight_mod[(size_t)row * B + k];
+  return u + 1e-7f;
+}
+
+// One Gaussian per thread, the track in passes of F frames: per pass the F frames' (G, q) records of every bone are staged in
+// LDS (64 B per bone and frame), a bone's weight is evaluated once and accumulated into F sets of 16 sums.  gridDim.y slices
+// the track where the Gaussians alone leave the device underfilled (each slice repeats the per-Gaussian prologue).
+// a.transforms / a.node_rot: (M, J, 12) / (M, J, 4) of the chain launch in front; a.d_xyz / a.d_rot: (M, N, 3) / (M, N, 4).
+template <bool TOPK, int MAXJ, int F>
+__global__ __launch_bounds__(256) void lbs_sequence_kernel(LbsArgs a, SeqArgs s) {
+  typedef std::conditional_t<(MAXJ > MAX_J) && TOPK, SelLds, SelReg> Sel;
+  __shared__ Bone bones[MAXJ - 1];
+  __shared__ float4 pose[F][MAXJ - 1][4];  // rows of [R|t] of the bone's child joint, then its node_rot
+  extern __shared__ float s_mod_dyn[];
+  const int B = a.J - 1, J = a.J;
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  const bool on = n < a.N;
+  const int row = min(n, a.N - 1);
+  const float px = a.x[3 * row], py = a.x[3 * row + 1], pz = a.x[3 * row + 2];
+  const float m = a.motion_mask ? a.motion_mask[row] : 1.0f;
+  int BP = 0;
+  const float* s_mod = stage_mod_tile(a, s_mod_dyn, BP);
+  stage_bone_geometry(a, bones);
+  Sel sel;
+  if constexpr (Sel::in_lds) {
+    __shared__ typename Sel::Column s_sel;
+    sel.col = s_sel;
+  }
+  if (TOPK) topk_select(sel, bones, B, a.K, px, py, pz);
+  const int f_begin = blockIdx.y * s.slice_frames, f_end = min(s.M, f_begin + s.slice_frames);
+  for (int f0 = f_begin; f0 < f_end; f0 += F) {
+    const int nf = min(F, f_end - f0);
+    __syncthreads();  // (the previous pass has read its records)
+    for (int e = threadIdx.x; e < F * B; e += 256) {
+      const int f = e / B, k = e - f * B;
+      float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0, q = g0;
+      if (f < nf) {
+        const size_t jf = (size_t)(f0 + f) * J + (k + 1);
+        const float4* G = reinterpret_cast<const float4*>(a.transforms + jf * 12);
+        g0 = G[0]; g1 = G[1]; g2 = G[2];
+        q = *reinterpret_cast<const float4*>(a.node_rot + jf * 4);
+      }
+      pose[f][k][0] = g0; pose[f][k][1] = g1; pose[f][k][2] = g2; pose[f][k][3] = q;
+    }
+    __syncthreads();
+    float acc[F][16], sum = 0.f;
+#pragma unroll
+    for (int f = 0; f < F; f++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[f][e] = 0.f;
+    for (int k = 0; k < B; k++) {
+      if (TOPK && !sel.test(k)) continue;
+      const float v = bone_weight<TOPK>(a, bones[k], k, B, row, s_mod, BP, px, py, pz);
+      sum += v;
+#pragma unroll
+      for (int f = 0; f < F; f++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const float4 g = pose[f][k][r];
+          acc[f][4 * r] += v * g.x; acc[f][4 * r + 1] += v * g.y; acc[f][4 * r + 2] += v * g.z; acc[f][4 * r + 3] += v * g.w;
+        }
+    }
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int f = 0; f < F; f++) {
+      if (!on || f >= nf) continue;
+      const float* gt = a.global_trans + (size_t)(f0 + f) * s.gt_stride;
+      const float* A = acc[f];
+      const float ax = (A[0] * px + A[1] * py + A[2] * pz + A[3]) * inv + gt[0];
+      const float ay = (A[4] * px + A[5] * py + A[6] * pz + A[7]) * inv + gt[1];
+      const float az = (A[8] * px + A[9] * py + A[10] * pz + A[11]) * inv + gt[2];
+      const size_t o = (size_t)(f0 + f) * a.N + n;
+      a.d_xyz[3 * o] = (ax - px) * m; a.d_xyz[3 * o + 1] = (ay - py) * m; a.d_xyz[3 * o + 2] = (az - pz) * m;
+      reinterpret_cast<float4*>(a.d_rot)[o] = make_float4(A[12] * inv * m, A[13] * inv * m, A[14] * inv * m, A[15] * inv * m);
+    }
+  }
+}
+
+// The skinning weights folded into a colour per Gaussian (visualization.py:118-129), nothing of (N, J-1) written:
+// mode 0 "blend"   sum_k w_k colour[k + 1]  (bone k <-> child joint k + 1);
+// mode 1 "segment" the colour of the bone of the largest weight, the first such bone on equality — a gathered value, unchanged.
+template <bool TOPK, int MAXJ>
+__global__ __launch_bounds__(256) void skinning_colors_kernel(LbsArgs a, const float* __restrict__ node_colors, int mode,
+                                                              float* __restrict__ out) {
+  typedef std::conditional_t<(MAXJ > MAX_J) && TOPK, SelLds, SelReg> Sel;
+  __shared__ Bone bones[MAXJ - 1];
+  __shared__ float s_col[MAXJ - 1][3];
+  extern __shared__ float s_mod_dyn[];
+  const int B = a.J - 1;
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  const int row = min(n, a.N - 1);
+  const float px = a.x[3 * row], py = a.x[3 * row + 1], pz = a.x[3 * row + 2];
+  int BP = 0;
+  const float* s_mod = stage_mod_tile(a, s_mod_dyn, BP);
+  for (int e = threadIdx.x; e < 3 * B; e += 256) (&s_col[0][0])[e] = node_colors[3 + e];
+  stage_bone_geometry(a, bones);
+  if (n >= a.N) return;
+  Sel sel;
+  if constexpr (Sel::in_lds) {
+    __shared__ typename Sel::Column s_sel;
+    sel.col = s_sel;
+  }
+  if (TOPK) topk_select(sel, bones, B, a.K, px, py, pz);
+  float c0 = 0.f, c1 = 0.f, c2 = 0.f, sum = 0.f, best = -1.0f;
+  int bi = 0;
+  for (int k = 0; k < B; k++) {
+    if (TOPK && !sel.test(k)) continue;
+    const float v = bone_weight<TOPK>(a, bones[k], k, B, row, s_mod, BP, px, py, pz);
+    sum += v;
+    c0 += v * s_col[k][0]; c1 += v * s_col[k][1]; c2 += v * s_col[k][2];
+    if (v > best) { best = v; bi = k; }
+  }
+  if (mode == 1) {
+    out[3 * n] = s_col[bi][0]; out[3 * n + 1] = s_col[bi][1]; out[3 * n + 2] = s_col[bi][2];
+  } else {
+    const float inv = 1.0f / sum;
+    out[3 * n] = c0 * inv; out[3 * n + 1] = c1 * inv; out[3 * n + 2] = c2 * inv;
+  }
+}
+
 }  // namespace riggs
 
 using namespace riggs;
@@ -1339,6 +1564,121 @@ int riggs_lbs_backward(int32_t N, int32_t J, int32_t K, const float* x, const fl
       case 7: launch_lbs_bwd_bonelane<7>(a, s); break;
       default: launch_lbs_bwd_bonelane<8>(a, s); break;
     }
+  }
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- playback: the launches
+// Frames per pass, by joint range.  A workgroup's static LDS stays within 64 KB: the bones' records (112 B each), F pose records
+// per bone (64 B each) and, for the top-K form beyond 64 joints, the 8 KB of selection columns —
+//   <= 64 joints  F = 4:  7.1 + 16.1 KB        (F = 4: the weight — ~20 vector instructions and an exp — is then a fifth of a
+//   <= 128 joints F = 4: 14.2 + 32.5 (+ 8) KB   bone's 64 multiply-adds, and 64 sums leave the kernel four waves per SIMD)
+//   <= 256 joints F = 2: 28.6 + 32.6 KB; top-K F = 1: 28.6 + 16.3 + 8 KB
+static int seq_pass_frames(int J, int K) { return J <= 128 ? 4 : (K > 0 ? 1 : 2); }
+template <bool TOPK, int MAXJ, int F>
+static constexpr size_t seq_static_lds() {
+  return sizeof(Bone) * (MAXJ - 1) + sizeof(float4) * 4 * F * (MAXJ - 1) + ((MAXJ > MAX_J && TOPK) ? sizeof(SelLds::Column) : 0);
+}
+static_assert(seq_static_lds<true, MAX_J, 4>() <= 65536 && seq_static_lds<true, 128, 4>() <= 65536 &&
+              seq_static_lds<false, MAX_J_WIDE, 2>() <= 65536 && seq_static_lds<true, MAX_J_WIDE, 1>() <= 65536, "64 KB of static LDS");
+// the weight_mod tile (256 (B | 1) floats, dynamic) where it fits beside `static_bytes` in 64 KB
+static size_t seq_mod_lds(LbsArgs& a, size_t static_bytes) {
+  const size_t tile = (size_t)256 * ((a.J - 1) | 1) * sizeof(float);
+  a.mod_lds = (a.weight_mod && static_bytes + tile <= 65536) ? 1 : 0;
+  return a.mod_lds ? tile : 0;
+}
+template <bool TOPK, int MAXJ, int F>
+static void launch_lbs_sequence(LbsArgs& a, const SeqArgs& s, dim3 grid, hipStream_t st) {
+  const size_t lds = seq_mod_lds(a, seq_static_lds<TOPK, MAXJ, F>());
+  hipLaunchKernelGGL((lbs_sequence_kernel<TOPK, MAXJ, F>), grid, dim3(256), lds, st, a, s);
+}
+template <bool TOPK, int MAXJ>
+static void launch_skinning_colors(LbsArgs& a, const float* node_colors, int mode, float* out, hipStream_t st) {
+  const size_t fixed = sizeof(Bone) * (MAXJ - 1) + 12 * (MAXJ - 1) + ((MAXJ > MAX_J && TOPK) ? sizeof(SelLds::Column) : 0);
+  const size_t lds = seq_mod_lds(a, fixed);
+  hipLaunchKernelGGL((skinning_colors_kernel<TOPK, MAXJ>), dim3(lbs_grid(a.N, 1)), dim3(256), lds, st, a, node_colors, mode, out);
+}
+
+// the current device's compute units, asked once per device ordinal (two runtime calls off the per-chunk path)
+static int seq_compute_units(int& cus) {
+  static int cached[64];  // 0: not asked yet
+  int dev = 0;
+  RIGGS_HIP_CHECK(hipGetDevice(&dev));
+  int& c = cached[dev & 63];
+  if (c <= 0) RIGGS_HIP_CHECK(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
+  cus = c;
+  return 0;
+}
+
+extern "C" {
+
+int32_t riggs_lbs_sequence_pass_frames(int32_t J, int32_t K) { return seq_pass_frames(J, K); }
+
+int riggs_lbs_sequence_forward(int32_t N, int32_t M, int32_t J, int32_t K, const float* x, const float* joints, const int32_t* parents,
+                               const float* node_radius_log, const float* local_rot, const float* global_trans,
+                               int32_t global_trans_stride, const float* motion_mask, const float* weight_mod, float* transforms,
+                               float* node_rot, float* d_nodes, float* d_xyz, float* d_rotation, riggs_stream stream) {
+  LbsArgs a;
+  int rc = fill_lbs(a, N, J, K, x, joints, parents, node_radius_log, transforms, node_rot, global_trans, motion_mask);
+  if (rc) return rc;
+  RIGGS_REQUIRE(M >= 0, "num_frames < 0");
+  RIGGS_REQUIRE(global_trans_stride == 0 || global_trans_stride == 3, "global_trans_stride must be 3 (per frame) or 0 (one for the track)");
+  RIGGS_REQUIRE(weight_mod == nullptr || K <= 0, "weight_mod is supported with K = -1 (all bones) only");
+  RIGGS_REQUIRE(local_rot && transforms && node_rot && d_nodes, "riggs_lbs_sequence_forward needs the poses and the three chain outputs");
+  a.d_xyz = d_xyz; a.d_rot = d_rotation; a.weight_mod = weight_mod;
+  if (M == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (J <= MAX_J) hipLaunchKernelGGL(fk_sequence_kernel, dim3(M), dim3(64), 0, st, J, global_trans_stride, local_rot, joints, parents,
+                                     global_trans, transforms, node_rot, d_nodes);
+  else hipLaunchKernelGGL(fk_sequence_wide_kernel, dim3(M), dim3(256), 0, st, J, global_trans_stride, local_rot, joints, parents,
+                          global_trans, transforms, node_rot, d_nodes);
+  RIGGS_HIP_CHECK(hipGetLastError());
+  if (N == 0) return 0;
+  // The grid: ceil(N / 256) workgroups walk the whole track each.  Where that is fewer than two workgroups per compute unit
+  // (eight waves: two per SIMD, the least that overlaps one wave's LDS reads with another's arithmetic), the track's passes are
+  // dealt over gridDim.y until it is — each slice pays the per-Gaussian prologue again, so no further.
+  const int F = seq_pass_frames(J, K);
+  const int passes = (M + F - 1) / F, blocks_x = (int)lbs_grid(N, 1);
+  int cus = 0;
+  if (seq_compute_units(cus)) return 1;
+  int slices = (2 * cus + blocks_x - 1) / blocks_x;
+  if (slices < 1) slices = 1;
+  if (slices > passes) slices = passes;
+  const int slice_passes = (passes + slices - 1) / slices;
+  SeqArgs s;
+  s.M = M; s.slice_frames = slice_passes * F; s.gt_stride = global_trans_stride;
+  const dim3 grid(blocks_x, (passes + slice_passes - 1) / slice_passes);
+  // (not under a ProfScope: the profiler's skinning slot is the per-frame forward's)
+  if (J <= MAX_J) {
+    if (K > 0) launch_lbs_sequence<true, MAX_J, 4>(a, s, grid, st); else launch_lbs_sequence<false, MAX_J, 4>(a, s, grid, st);
+  } else if (J <= 128) {
+    if (K > 0) launch_lbs_sequence<true, 128, 4>(a, s, grid, st); else launch_lbs_sequence<false, 128, 4>(a, s, grid, st);
+  } else {
+    if (K > 0) launch_lbs_sequence<true, MAX_J_WIDE, 1>(a, s, grid, st); else launch_lbs_sequence<false, MAX_J_WIDE, 2>(a, s, grid, st);
+  }
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int riggs_skinning_colors(int32_t N, int32_t J, int32_t K, const float* x, const float* joints, const int32_t* parents,
+                          const float* node_radius_log, const float* weight_mod, const float* node_colors, int32_t mode,
+                          float* colors, riggs_stream stream) {
+  LbsArgs a;
+  int rc = fill_lbs(a, N, J, K, x, joints, parents, node_radius_log, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  RIGGS_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (blend) or 1 (segment)");
+  RIGGS_REQUIRE(weight_mod == nullptr || K <= 0, "weight_mod is supported with K = -1 (all bones) only");
+  RIGGS_REQUIRE(node_colors && colors, "riggs_skinning_colors needs the node colours and the output");
+  a.weight_mod = weight_mod;
+  if (N == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (J <= MAX_J) {
+    if (K > 0) launch_skinning_colors<true, MAX_J>(a, node_colors, mode, colors, st); else launch_skinning_colors<false, MAX_J>(a, node_colors, mode, colors, st);
+  } else {
+    if (K > 0) launch_skinning_colors<true, MAX_J_WIDE>(a, node_colors, mode, colors, st); else launch_skinning_colors<false, MAX_J_WIDE>(a, node_colors, mode, colors, st);
   }
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;

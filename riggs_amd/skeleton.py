@@ -814,6 +814,15 @@ class SkeletonWarp(NodeGaussians, nn.Module):
              "d_nodes": d_nodes, "nn_idx": None, "nn_weight": None, "local_rotation": node_attrs["local_rotation"],
              "global_trans": global_trans, "d_opacity": None, "d_color": None}, producer=producer)
 
+    # ---- playback (riggs_amd/playback.py): a pose track over one canonical cloud, the colours of the skinning-weight view
+    def deform_sequence(self, x, poses, motion_mask):
+        from .playback import deform_sequence
+        return deform_sequence(self, x, poses, motion_mask)
+
+    def skinning_colors(self, x, mode="blend"):
+        from .playback import skinning_colors
+        return skinning_colors(self, x, mode)
+
     def node_deformation(self, x, node_attrs):
         x = x.detach()
         joints = self._joints()
