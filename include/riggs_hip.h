@@ -1018,6 +1018,27 @@ size_t riggs_fps_rows_workspace_bytes(int32_t N, int32_t D);
 int riggs_fps_sample_rows(int32_t N, int32_t D, int32_t npoint, const float* rows, int64_t row_stride, const int64_t* start,
                           void* workspace, int64_t* out_indices, riggs_stream stream);
 
+/* =====================================================================
+ * Evaluation report: L1, PSNR, SSIM and MS-SSIM of B frames (C, H, W) against their ground truth, as train_utils.py:56-243 and
+ * render_rig.py:111-218 report them.  SSIM is piq.ssim(x, y, data_range=1.): mean pool by f = max(1, round(min(H, W) / 256))
+ * (half to even), then one level with a VALID 11 x 11 Gaussian window (sigma 1.5), mean of ssim_map over the outputs and the
+ * channels.  MS-SSIM is pytorch_msssim.ms_ssim(X, Y, data_range=1.): five such levels with a 2 x 2 mean pool (h % 2, w % 2 zeros
+ * in front, counted in the divisor) between them, prod_l relu(v_l) ^ wt_l per channel (v = the cs mean of levels 0..3 and the
+ * ssim mean of level 4; wt = 0.0448, 0.2856, 0.3001, 0.2363, 0.1333), mean over channels; needs min(H, W) > 160.  Both are
+ * restated from the packages' published algorithms.  PSNR = 20 log10(1 / sqrt(mean (x - y)^2)) per frame (inf for identical
+ * images), L1 = mean |x - y|.  clamp != 0 clamps both inputs to [0, 1] first (the reference's torch.clamp before its metrics).
+ * out: (B, 4) = {l1, psnr, ssim, ms_ssim} per frame (ms_ssim = NaN unless want_ms_ssim).  levels_or_null: (B, 6, C, 2) =
+ * {ssim mean, cs mean} of the five MS-SSIM levels and of the piq level (NaN for a level the call did not compute).
+ * workspace: riggs_image_metrics_workspace_floats(B, C, H, W) floats, 8-byte aligned.  Every sum is formed in a fixed order in
+ * float64: a frame's row does not depend on B or on the other frames.  All launches go on `stream`; nothing synchronises.
+ * Rejected before any HIP call (non-zero status, riggs_last_error): B < 1 or C < 1, a NULL x / y / out / workspace, a workspace
+ * that is too small, want_ms_ssim with min(H, W) <= 160, an SSIM level smaller than 11 on a side after pooling.
+ * ===================================================================== */
+size_t riggs_image_metrics_workspace_floats(int32_t B, int32_t C, int32_t H, int32_t W);
+int riggs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float* x, const float* y, int32_t clamp,
+                        int32_t want_ms_ssim, float* out, float* levels_or_null, float* workspace, size_t workspace_floats,
+                        riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

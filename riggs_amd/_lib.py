@@ -281,6 +281,8 @@ _SIGS = {
     "riggs_fps_sample": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     "riggs_fps_rows_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "riggs_fps_sample_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
+    "riggs_image_metrics_workspace_floats": (C.c_size_t, [C.c_int32] * 4),
+    "riggs_image_metrics": (C.c_int, [C.c_int32] * 4 + [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
 }
 
 

@@ -39,6 +39,10 @@ SOURCES = {
     "flow.hip": ["-ffp-contract=off"],  # (the loss forms fl(w c) - fl(w m) as the reference does: no fused multiply-subtract)
     "fps.hip": ["-ffp-contract=off"],  # (the squared distance is fl(fl(dx dx + dy dy) + dz dz), as torch.sum gives it on the CPU)
     "playback.hip": ["-ffp-contract=off"],  # (slerp / lerp in the reference's own steps: one rounding per operation)
+    # metrics.hip: its taps are explicit FMAs either way; contraction turns the cancelling E[x^2] - mu^2 of the epilogue into one
+    # fused multiply-subtract (mu^2 is not rounded before the subtraction): never less accurate against the float64 definition,
+    # which is what its tests compare with — no CPU oracle has to be matched bit for bit here.
+    "metrics.hip": ["-ffp-contract=fast"],
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

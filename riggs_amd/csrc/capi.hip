@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "metrics.h"
 #include "raster_internal.h"
 
 namespace riggs {
@@ -443,6 +444,31 @@ int riggs_raster_backward(const riggs_raster_cfg* cfg, const float* means3D, con
   { ProfScope ps(PROF_PREPROCESS_BWD, s); launch_preprocess_bwd(b, s); }
   if (debug_sync(cfg->debug, s, "preprocess_bwd")) return 1;
   return 0;
+}
+
+// ---- evaluation report (csrc/metrics.hip) ------------------------------------------------------------------------------------
+size_t riggs_image_metrics_workspace_floats(int32_t B, int32_t C, int32_t H, int32_t W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1 || (int64_t)B * C > INT32_MAX) return 0;
+  return metrics_plan(B, C, H, W).total_floats;
+}
+
+int riggs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float* x, const float* y, int32_t clamp,
+                        int32_t want_ms_ssim, float* out, float* levels_or_null, float* workspace, size_t workspace_floats,
+                        riggs_stream stream) {
+  RIGGS_REQUIRE(B >= 1 && C >= 1, "riggs_image_metrics: B and C must be at least 1");
+  RIGGS_REQUIRE(H >= 1 && W >= 1 && (int64_t)B * C <= INT32_MAX, "riggs_image_metrics: bad image shape");
+  RIGGS_REQUIRE(x && y && out && workspace, "riggs_image_metrics: NULL buffer");
+  RIGGS_REQUIRE(((uintptr_t)workspace & 7) == 0, "riggs_image_metrics: the workspace must be 8-byte aligned");
+  const MetricsPlan p = metrics_plan(B, C, H, W);
+  if (workspace_floats < p.total_floats) {
+    set_error("riggs_image_metrics: the workspace (%zu floats) is smaller than riggs_image_metrics_workspace_floats(%d, %d, %d, %d) = %zu",
+              workspace_floats, B, C, H, W, p.total_floats);
+    return 2;
+  }
+  RIGGS_REQUIRE(!want_ms_ssim || p.ms, "riggs_image_metrics: MS-SSIM needs min(H, W) > 160 (five levels of an 11-tap window)");
+  RIGGS_REQUIRE(p.h[5] >= 11 && p.w[5] >= 11, "riggs_image_metrics: the SSIM level is smaller than the 11 x 11 window");
+  return launch_image_metrics(p, B, C, H, W, x, y, clamp ? 1 : 0, want_ms_ssim ? 1 : 0, out, levels_or_null, workspace,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"
