@@ -140,5 +140,10 @@ __device__ __forceinline__ float wave_sum_bcast(float v) {
   v = wave_sum(v);
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// float64: butterfly, the sum in every lane.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 }  // namespace riggs

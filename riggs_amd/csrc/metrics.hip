@@ -16,26 +16,16 @@
 // (frame, channel)'s partials in a fixed order.  No float atomics: a frame's numbers do not depend on B, on its neighbours in the
 // batch or on the run.
 #include "metrics.h"
+#include "ssim_window.h"
 
 namespace riggs {
 
-#define MT_T 32             // output tile: 32 columns ...
-#define MT_TH 64            // ... x 64 rows, 512 threads, 4 outputs each in either pass (the tall tile of csrc/loss.hip)
-#define MT_NT 512
-#define MT_TAPS 11
-#define MT_A (MT_TAPS - 1)  // apron: 10 pixels to the right and below
-#define MT_S (MT_T + MT_A)  // staged columns: 42
-#define MT_SH (MT_TH + MT_A)  // staged rows: 74
-#define MT_PX 44            // row pitch of the staged pairs (in pairs): rows start 16-byte aligned
 #define MT_PLANES_PER_LAUNCH 65535
 // The variances and the covariance do not change when a constant is taken off both images; E[x^2] - mu^2 loses the fewer bits the
 // smaller E[x^2] is.  Images live in [0, 1]: the moments are formed of x - 0.5 and y - 0.5 (an exact subtraction for x >= 0.25),
 // which cut the deviation from the float64 definition about tenfold on the test images; mu = (G*(x - 0.5)) + 0.5 for the
 // luminance term.  L1 and the squared error are formed of the unshifted values.
 #define MT_SHIFT 0.5f
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2v pk_fma(float w, f2v a, f2v c) { return __builtin_elementwise_fma(f2v{w, w}, a, c); }
 
 struct LevelArgs {
   int h, w;         // this level's image size
@@ -44,23 +34,19 @@ struct LevelArgs {
   int first;        // level 0: also sum |x - y| and (x - y)^2, every input pixel by the workgroup that owns it
   const float *x, *y;  // (planes, h, w)
   double* partial;     // [plane][workgroup][4]: sum ssim_map, sum cs_map, sum |x - y|, sum (x - y)^2
-  float win[MT_TAPS];
+  float win[SW_TAPS];
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__global__ __launch_bounds__(MT_NT) void metrics_level_kernel(LevelArgs a) {
-  // Packed fp32 as in the loss kernel: the staged images travel as (x, y) pairs, the moments as (mu1, mu2), (E[x^2], E[y^2]) and
-  // the lone E[xy]; a thread produces 4 adjacent outputs from 14 staged inputs in either pass.  75 KB of LDS: two workgroups per CU.
-  __shared__ f2v s_xy[MT_SH][MT_PX];
-  __shared__ f2v s_m[MT_SH][MT_T + 1], s_e[MT_SH][MT_T + 1];
-  __shared__ float s_c[MT_SH][MT_T + 1];
-  __shared__ double s_red[4][MT_NT / 64];
-  const int tx0 = blockIdx.x * MT_T, ty0 = blockIdx.y * MT_TH;
+__global__ __launch_bounds__(SW_NT) void metrics_level_kernel(LevelArgs a) {
+  __shared__ f2v s_xy[SW_SH][SW_PX];
+  __shared__ f2v s_m[SW_SH][SW_PH], s_e[SW_SH][SW_PH];
+  __shared__ float s_c[SW_SH][SW_PH];
+  __shared__ double s_red[4][SW_NT / 64];
+  const int tx0 = blockIdx.x * SW_T, ty0 = blockIdx.y * SW_TH;
   const int tid = threadIdx.x;
+  // (read once, here: when the staging functors read them through the captured argument struct, THIS kernel loaded them again
+  // behind the barriers and its vertical pass waited for the LDS more coarsely; the loss kernels capture theirs without such an effect)
+  const int h = a.h, w = a.w, clamp = a.clamp, first = a.first;
   const size_t plane = (size_t)a.plane0 + blockIdx.z;
   const float* X = a.x + plane * a.h * a.w;
   const float* Y = a.y + plane * a.h * a.w;
@@ -68,92 +54,51 @@ __global__ __launch_bounds__(MT_NT) void metrics_level_kernel(LevelArgs a) {
   // apron, which ends at or before the image's edge there (the outputs end 10 pixels before it).
   const bool last_x = blockIdx.x == gridDim.x - 1, last_y = blockIdx.y == gridDim.y - 1;
   double ad_sum = 0.0, sq_sum = 0.0;
-  {
-    constexpr int NST = (MT_SH * MT_S + MT_NT - 1) / MT_NT;
-    float gx[NST], gy[NST];
-#pragma unroll
-    for (int i = 0; i < NST; i++) {  // (all of the thread's loads in flight before the first LDS write)
-      const int e = tid + MT_NT * i, r = e / MT_S, q = e % MT_S;
-      const bool in = e < MT_SH * MT_S && ty0 + r < a.h && tx0 + q < a.w;
-      const size_t idx = (size_t)(ty0 + r) * a.w + (tx0 + q);
-      gx[i] = in ? X[idx] : 0.f;
-      gy[i] = in ? Y[idx] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < NST; i++) {
-      const int e = tid + MT_NT * i, r = e / MT_S, q = e % MT_S;
-      if (e < MT_SH * MT_S) {
-        float vx = gx[i], vy = gy[i];
-        if (a.clamp) { vx = fminf(fmaxf(vx, 0.f), 1.f); vy = fminf(fmaxf(vy, 0.f), 1.f); }
+  sw_stage<2, 0>(
+      tid, ty0, tx0,
+      [&](int yy, int xx, float(&g)[2]) {
+        const bool in = yy < h && xx < w;
+        const size_t idx = (size_t)yy * w + xx;
+        g[0] = in ? X[idx] : 0.f;
+        g[1] = in ? Y[idx] : 0.f;
+      },
+      [&](int r, int q, const float(&g)[2]) {
+        float vx = g[0], vy = g[1];
+        if (clamp) { vx = fminf(fmaxf(vx, 0.f), 1.f); vy = fminf(fmaxf(vy, 0.f), 1.f); }
         s_xy[r][q] = f2v{vx - MT_SHIFT, vy - MT_SHIFT};
-        const bool owned = ty0 + r < a.h && tx0 + q < a.w && (r < MT_TH || last_y) && (q < MT_T || last_x);
-        if (a.first && owned) {
+        const bool owned = ty0 + r < h && tx0 + q < w && (r < SW_TH || last_y) && (q < SW_T || last_x);
+        if (first && owned) {
           const float d = vx - vy, d2 = d * d;  // float32 difference and square, float64 sums
           ad_sum += (double)fabsf(d);
           sq_sum += (double)d2;
         }
-      }
-    }
-  }
+      });
   __syncthreads();
-  float win[MT_TAPS];
+  float win[SW_TAPS];
 #pragma unroll
-  for (int k = 0; k < MT_TAPS; k++) win[k] = a.win[k];
-  // horizontal pass: 74 rows x 8 groups of 4 columns
-  for (int e = tid; e < MT_SH * (MT_T / 4); e += MT_NT) {
-    const int r = e >> 3, q0 = (e & 7) * 4;
-    f2v p[14], pp[14];
-    float pc[14];
-#pragma unroll
-    for (int k = 0; k < 14; k++) {
-      p[k] = s_xy[r][q0 + k];
-      pp[k] = p[k] * p[k];
-      pc[k] = p[k].x * p[k].y;
-    }
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-      f2v m = f2v{0.f, 0.f}, ee = f2v{0.f, 0.f};
-      float e12 = 0.f;
-#pragma unroll
-      for (int k = 0; k < MT_TAPS; k++) {
-        m = pk_fma(win[k], p[o + k], m);
-        ee = pk_fma(win[k], pp[o + k], ee);
-        e12 = fmaf(win[k], pc[o + k], e12);
-      }
-      s_m[r][q0 + o] = m; s_e[r][q0 + o] = ee; s_c[r][q0 + o] = e12;
-    }
-  }
+  for (int k = 0; k < SW_TAPS; k++) win[k] = a.win[k];
+  sw_hpass(tid, [&](int r, int q0) { sw_row4_moments(win, s_xy, s_m, s_e, s_c, r, q0); });
   __syncthreads();
-  // vertical pass: thread = (column lx, 4 consecutive rows ly0..ly0+3)
-  const int lx = tid & 31, ly0 = (tid >> 5) * 4;
   double ssim_sum = 0.0, cs_sum = 0.0;
-  {
-    f2v cm[14], ce[14];
-    float cc[14];
+  const int px = tx0 + sw_lx(tid);
+  f2v cm[14], ce[14];
+  float cc[14];
+  sw_col14_moments(s_m, s_e, s_c, tid, cm, ce, cc);
 #pragma unroll
-    for (int k = 0; k < 14; k++) { cm[k] = s_m[ly0 + k][lx]; ce[k] = s_e[ly0 + k][lx]; cc[k] = s_c[ly0 + k][lx]; }
-    const int px = tx0 + lx;
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-      f2v m = f2v{0.f, 0.f}, ee = f2v{0.f, 0.f};
-      float e12 = 0.f;
-#pragma unroll
-      for (int k = 0; k < MT_TAPS; k++) {
-        m = pk_fma(win[k], cm[o + k], m);
-        ee = pk_fma(win[k], ce[o + k], ee);
-        e12 = fmaf(win[k], cc[o + k], e12);
-      }
-      const int py = ty0 + ly0 + o;
-      if (px < a.w - MT_A && py < a.h - MT_A) {
-        const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
-        const float s1 = ee.x - m.x * m.x, s2 = ee.y - m.y * m.y, s12 = e12 - m.x * m.y;  // (of the shifted images)
-        const float m1 = m.x + MT_SHIFT, m2 = m.y + MT_SHIFT;
-        const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
-        const float cs = (2.f * s12 + C2) / (s1 + s2 + C2);
-        const float ss = (2.f * mu12 + C1) / (mu1_sq + mu2_sq + C1) * cs;
-        ssim_sum += (double)ss;
-        cs_sum += (double)cs;
-      }
+  for (int o = 0; o < 4; o++) {
+    f2v m, ee;
+    float e12;
+    sw_tap_moments(win, cm, ce, cc, o, m, ee, e12);
+    const int py = ty0 + sw_ly0(tid) + o;
+    if (px < w - SW_A && py < h - SW_A) {
+      const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
+      const float s1 = ee.x - m.x * m.x, s2 = ee.y - m.y * m.y, s12 = e12 - m.x * m.y;  // (of the shifted images)
+      const float m1 = m.x + MT_SHIFT, m2 = m.y + MT_SHIFT;
+      const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
+      const float cs = (2.f * s12 + C2) / (s1 + s2 + C2);
+      const float ss = (2.f * mu12 + C1) / (mu1_sq + mu2_sq + C1) * cs;
+      ssim_sum += (double)ss;
+      cs_sum += (double)cs;
     }
   }
   const double r0 = wave_sum_f64(ssim_sum), r1 = wave_sum_f64(cs_sum), r2 = wave_sum_f64(ad_sum), r3 = wave_sum_f64(sq_sum);
@@ -161,7 +106,7 @@ __global__ __launch_bounds__(MT_NT) void metrics_level_kernel(LevelArgs a) {
   __syncthreads();
   if (tid < 4) {
     double t = 0.0;
-    for (int wv = 0; wv < MT_NT / 64; wv++) t += s_red[tid][wv];
+    for (int wv = 0; wv < SW_NT / 64; wv++) t += s_red[tid][wv];
     const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x, n_wg = (size_t)gridDim.x * gridDim.y;
     a.partial[(plane * n_wg + wg) * 4 + tid] = t;
   }
@@ -289,9 +234,9 @@ MetricsPlan metrics_plan(int B, int C, int H, int W) {
   p.h[5] = H / p.f; p.w[5] = W / p.f;
   size_t d = 0;
   for (int l = 0; l < MT_LEVELS; l++) {
-    const bool runs = p.h[l] >= MT_TAPS && p.w[l] >= MT_TAPS;
-    p.tx[l] = runs ? ceil_div(p.w[l] - MT_A, MT_T) : 0;
-    p.ty[l] = runs ? ceil_div(p.h[l] - MT_A, MT_TH) : 0;
+    const bool runs = p.h[l] >= SW_TAPS && p.w[l] >= SW_TAPS;
+    p.tx[l] = runs ? ceil_div(p.w[l] - SW_A, SW_T) : 0;
+    p.ty[l] = runs ? ceil_div(p.h[l] - SW_A, SW_TH) : 0;
     if (l == 5 && p.f == 1) { p.part[5] = p.part[0]; break; }  // the piq level is level 0
     p.part[l] = d;
     d += planes * p.tx[l] * p.ty[l] * 4;
@@ -306,13 +251,6 @@ MetricsPlan metrics_plan(int B, int C, int H, int W) {
   return p;
 }
 
-static void fill_window(float* win) {
-  // exp(-(k - 5)^2 / (2 1.5^2)) normalised to sum 1 in float64, then rounded
-  double g[MT_TAPS], s = 0.0;
-  for (int k = 0; k < MT_TAPS; k++) { g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); s += g[k]; }
-  for (int k = 0; k < MT_TAPS; k++) win[k] = (float)(g[k] / s);
-}
-
 int launch_image_metrics(const MetricsPlan& p, int B, int C, int H, int W, const float* x, const float* y, int clamp, int want_ms,
                          float* out, float* levels, float* workspace, hipStream_t s) {
   const size_t planes = (size_t)B * C;
@@ -320,11 +258,11 @@ int launch_image_metrics(const MetricsPlan& p, int B, int C, int H, int W, const
   auto level = [&](int l, const float* lx, const float* ly, int cl) {
     LevelArgs a;
     a.h = p.h[l]; a.w = p.w[l]; a.clamp = cl; a.first = l == 0; a.x = lx; a.y = ly; a.partial = partial + p.part[l];
-    fill_window(a.win);
+    fill_window_f64(a.win);
     for (size_t p0 = 0; p0 < planes; p0 += MT_PLANES_PER_LAUNCH) {
       const size_t n = planes - p0 < MT_PLANES_PER_LAUNCH ? planes - p0 : MT_PLANES_PER_LAUNCH;
       a.plane0 = (int)p0;
-      hipLaunchKernelGGL(metrics_level_kernel, dim3(p.tx[l], p.ty[l], (unsigned)n), dim3(MT_NT), 0, s, a);
+      hipLaunchKernelGGL(metrics_level_kernel, dim3(p.tx[l], p.ty[l], (unsigned)n), dim3(SW_NT), 0, s, a);
     }
   };
   auto pool = [&](int from, int to, int k, int ph, int pw, const float* sx, const float* sy, int cl) {
@@ -359,7 +297,7 @@ int launch_image_metrics(const MetricsPlan& p, int B, int C, int H, int W, const
   for (int l = 0; l < MT_LEVELS; l++) {
     fa.n_wg[l] = p.tx[l] * p.ty[l];
     fa.part[l] = p.part[l];
-    fa.count[l] = (double)(p.h[l] - MT_A) * (double)(p.w[l] - MT_A);
+    fa.count[l] = (double)(p.h[l] - SW_A) * (double)(p.w[l] - SW_A);
   }
   if (p.f == 1) fa.n_wg[5] = fa.n_wg[0];
   hipLaunchKernelGGL(metrics_finalise_kernel, dim3(B), dim3(MT_FIN_NT), 0, s, fa);

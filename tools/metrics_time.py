@@ -4,8 +4,9 @@ packages issue — at (3, 800, 800) with B = 1 and B = 20 frames, and ``evaluate
 against the per-frame loop (``chunk=1``: one call per frame, as the reference scores its frames).
 
 Device time by events around a loop of calls after a warm-up; the median of repeated windows.  Launch counts from the
-profiler's device-side events in an untimed pass.  Writes profiles/metrics_times.json (or the path after --out).  Needs the GPU:
-there is no CPU fallback."""
+profiler's device-side events in an untimed pass.  Writes profiles/metrics_times.json (or the path after --out); ``--lib PATH``
+loads that libriggs_hip.so instead of the tree's (two builds are compared each in a process of its own) and ``--legs image_metrics``
+leaves the ``evaluate`` leg out.  Needs the GPU: there is no CPU fallback."""
 import json
 import os
 import statistics
@@ -16,6 +17,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from riggs_amd import _lib  # noqa: E402
+
+if "--lib" in sys.argv:
+    _lib.SO_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])  # (before the first lib() call)
 
 from riggs_amd import metrics as M  # noqa: E402
 from riggs_amd import synth  # noqa: E402
@@ -113,8 +119,13 @@ def evaluate_leg(n_cams=20, N=100_000, J=24):
 
 def main():
     assert torch.cuda.is_available(), "metrics_time.py measures on the GPU"
+    legs = sys.argv[sys.argv.index("--legs") + 1].split(",") if "--legs" in sys.argv else ["image_metrics", "evaluate"]
     out = {"what": "evaluation report at (%d, %d, %d); per call" % (C, H, W), "device": torch.cuda.get_device_name(0),
-           "image_metrics": report_legs(), "evaluate": evaluate_leg()}
+           "library": _lib.SO_PATH}
+    if "image_metrics" in legs:
+        out["image_metrics"] = report_legs()
+    if "evaluate" in legs:
+        out["evaluate"] = evaluate_leg()
     for k, v in out.items():
         print(k, json.dumps(v))
     path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "metrics_times.json")
