@@ -1039,6 +1039,91 @@ int riggs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float*
                         int32_t want_ms_ssim, float* out, float* levels_or_null, float* workspace, size_t workspace_floats,
                         riggs_stream stream);
 
+/* =====================================================================
+ * The editor's display frame (riggs_amd/viewer.py): interactive_GUI.py::test_step :497-664 with its overlay builders :97-247,
+ * render_rig.py::project_nodes_to_2d_withnodes :40-94 and utils/other_utils.py::depth2normal :78-97.  Inference only; every
+ * launch goes on `stream`, nothing synchronises.  Added symbols: riggs_version() is unchanged.
+ *
+ * A PRIMITIVE is RIGGS_VIEWER_PRIM_WORDS = 12 32-bit words: [0] kind (segment / disc / axis-aligned square), [1..4] the integer
+ * end points x0 y0 x1 y1 (a disc's centre twice; a square's left_top and right_bottom), [5] the DOUBLED extent of the colour
+ * shape and [6] of the alpha shape (a segment's thickness t, a disc's 2 r; unused by squares), [7..9] rgb as float bits, [10]
+ * valid, [11] reserved (0).  A table lists primitives in paint order; the last writer wins.
+ *
+ * COVERAGE.  OpenCV's own scan conversion is not restated; the rule is geometric.  The pixel at integer (x, y) is inside
+ *   a disc of radius r at the integer centre c     iff  dx^2 + dy^2 <= r^2;
+ *   a square                                        iff  x0 <= x <= x1 and y0 <= y <= y1 (the reference's left_top .. right_bottom);
+ *   a segment of thickness t                        iff  its squared distance to the CLOSED segment is <= (t / 2)^2 (round caps);
+ *   a zero-length segment is a disc of radius t / 2.
+ * With e2 the doubled extent this is evaluated in integers as 4 d^2 <= e2^2 against an end point (or the centre) and
+ * 4 cross^2 <= e2^2 |b - a|^2 against the body.  Coordinates are clamped to +-RIGGS_VIEWER_COORD_MAX = 8192 (which only moves
+ * end points that lie that far off screen; the window is at most that large) and e2 <= RIGGS_VIEWER_EXT2_MAX = 4096, so every
+ * product stays below 2^61: exact in int64.  A primitive with a non-finite coordinate or w <= 0 (z <= 0 under the render_rig
+ * rule) is marked invalid and never drawn — a deviation: OpenCV would draw garbage there.
+ * ===================================================================== */
+#define RIGGS_VIEWER_PRIM_WORDS 12
+#define RIGGS_VIEWER_COORD_MAX 8192
+#define RIGGS_VIEWER_EXT2_MAX 4096
+#define RIGGS_VIEWER_MAX_TABLES 8
+#define RIGGS_VIEWER_RANGE_WORKSPACE_FLOATS 512
+enum { RIGGS_VIEWER_SEGMENT = 0, RIGGS_VIEWER_DISC = 1, RIGGS_VIEWER_SQUARE = 2 };
+enum { RIGGS_VIEWER_RULE_EDITOR = 0, RIGGS_VIEWER_RULE_RENDER_RIG = 1 };
+enum { RIGGS_VIEWER_LAYOUT_SKELETON = 0, RIGGS_VIEWER_LAYOUT_SQUARES = 1, RIGGS_VIEWER_LAYOUT_POLYLINES = 2 };
+enum { RIGGS_VIEWER_MODE_IMAGE = 0, RIGGS_VIEWER_MODE_DEPTH = 1, RIGGS_VIEWER_MODE_ALPHA = 2, RIGGS_VIEWER_MODE_NORMAL = 3 };
+enum { RIGGS_VIEWER_BLEND_ALPHA = 0, RIGGS_VIEWER_BLEND_MASK = 1 };
+
+/* min and max of n floats into out_min_max[0], [1]: two fixed-order stages, no atomics; exact, a NaN wins as in torch.min / max.
+ * workspace: RIGGS_VIEWER_RANGE_WORKSPACE_FLOATS floats. */
+int riggs_viewer_depth_range(int64_t n, const float* depth, float* workspace, float* out_min_max, riggs_stream stream);
+
+/* depth2normal: depth (h, w) -> out (3, h, w), unit normals; focal as the reference's default w / 2 / tan(pi / 6) or given. */
+int riggs_viewer_depth2normal(int32_t h, int32_t w, const float* depth, float focal, float* out, riggs_stream stream);
+
+/* Points -> primitives, one launch.  rule EDITOR: uv = (p_hom @ matrix)[:2] / w with matrix = full_proj_transform, then
+ * (uv + 1) / 2 * [scale_x, scale_y] where the reference passes scale_x = image_height and scale_y = image_width (x scaled by the
+ * HEIGHT: kept); RENDER_RIG: matrix = world_view_transform, fx x / z + cx + 0.5 and fy y / z + cy + 0.5.  Both truncate toward
+ * zero.  Layouts (the count is riggs_viewer_project_count):
+ *   SKELETON   points (n, 3), parents (n): n - 1 segments (joint i -> parents[i], i >= 1; colour rgb[0..2], thickness
+ *              segment_ext2) and n discs (colours[i] or rgb[3..5]; doubled radii disc_color_ext2 / disc_alpha_ext2); the segments
+ *              come first unless discs_first.  uv, if given, receives the n un-truncated coordinates (n, 2).
+ *   SQUARES    points (n, 3): trunc(uv - square_radius) .. trunc(uv + square_radius), colours[i] or rgb[0..2]; uv as above.
+ *   POLYLINES  points (ring_capacity, n, 3), a ring of samples whose oldest is slot ring_head: for each of the n tracks the
+ *              samples - 1 segments between consecutive samples, track after track; colours[track] or rgb[0..2].
+ * table may be NULL when only uv is wanted. */
+typedef struct riggs_viewer_projection {
+  int32_t layout, rule, n, samples, ring_head, ring_capacity, discs_first;
+  int32_t segment_ext2, disc_color_ext2, disc_alpha_ext2, square_radius, reserved;
+  const float* points;
+  const int32_t* parents;
+  const float* matrix; /* (4, 4) row-major, on the device */
+  const float* colors; /* or NULL */
+  float scale_x, scale_y, fx, fy, cx, cy;
+  float rgb[6];
+  int32_t* table;
+  float* uv;
+} riggs_viewer_projection;
+int64_t riggs_viewer_project_count(const riggs_viewer_projection* p);
+int riggs_viewer_project(const riggs_viewer_projection* p, riggs_stream stream);
+
+/* The display frame, one launch (a 16 x 16 tile per workgroup).  Base colour by mode — IMAGE: source (3, h, w); DEPTH: source
+ * (1, h, w) as (d - min) / (max - min + 1e-20) with range = {min, max} on the device; ALPHA: source (1, h, w) replicated; NORMAL:
+ * (depth2normal(source) + 1) / 2, evaluated at the source pixels the taps read — then F.interpolate(mode="bilinear",
+ * align_corners=False) to (height, width) (scale_h = h / height and scale_w = w / width, in float) and a clamp to [0, 1].  The
+ * tables are then painted one after another: per table a colour layer (rgb where the pixel is in a primitive's colour shape) and
+ * an alpha layer (1 where it is in its alpha shape), then BLEND_ALPHA: out = base (1 - a) + rgb a, or BLEND_MASK:
+ * out = base (sum(rgb) == 0) + rgb.  out: (height, width, 3) float32. */
+typedef struct riggs_viewer_frame {
+  int32_t mode, src_height, src_width, height, width, num_tables;
+  float focal, scale_h, scale_w;
+  int32_t reserved;
+  const float* source;
+  const float* range;
+  const int32_t* tables[RIGGS_VIEWER_MAX_TABLES];
+  int32_t counts[RIGGS_VIEWER_MAX_TABLES];
+  int32_t rules[RIGGS_VIEWER_MAX_TABLES];
+  float* out;
+} riggs_viewer_frame;
+int riggs_viewer_compose(const riggs_viewer_frame* f, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

@@ -150,6 +150,21 @@ class NodeMlpGrads(C.Structure):
                 ("w", _P * 8), ("b", _P * 8), ("head_w", _P * 5), ("head_b", _P * 5)]
 
 
+class ViewerProjection(C.Structure):
+    """riggs_viewer_projection (include/riggs_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("layout", "rule", "n", "samples", "ring_head", "ring_capacity", "discs_first", "segment_ext2",
+                                         "disc_color_ext2", "disc_alpha_ext2", "square_radius", "reserved")] + \
+               [("points", _P), ("parents", _P), ("matrix", _P), ("colors", _P)] + \
+               [(n, C.c_float) for n in ("scale_x", "scale_y", "fx", "fy", "cx", "cy")] + [("rgb", C.c_float * 6), ("table", _P), ("uv", _P)]
+
+
+class ViewerFrame(C.Structure):
+    """riggs_viewer_frame (include/riggs_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("mode", "src_height", "src_width", "height", "width", "num_tables")] + \
+               [("focal", C.c_float), ("scale_h", C.c_float), ("scale_w", C.c_float), ("reserved", C.c_int32), ("source", _P), ("range", _P),
+                ("tables", _P * 8), ("counts", C.c_int32 * 8), ("rules", C.c_int32 * 8), ("out", _P)]
+
+
 _SIGS = {
     "riggs_version": (C.c_int, []),
     "riggs_last_error": (C.c_char_p, []),
@@ -283,6 +298,11 @@ _SIGS = {
     "riggs_fps_sample_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     "riggs_image_metrics_workspace_floats": (C.c_size_t, [C.c_int32] * 4),
     "riggs_image_metrics": (C.c_int, [C.c_int32] * 4 + [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    "riggs_viewer_depth_range": (C.c_int, [C.c_int64, _P, _P, _P, _P]),
+    "riggs_viewer_depth2normal": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_float, _P, _P]),
+    "riggs_viewer_project_count": (C.c_int64, [C.POINTER(ViewerProjection)]),
+    "riggs_viewer_project": (C.c_int, [C.POINTER(ViewerProjection), _P]),
+    "riggs_viewer_compose": (C.c_int, [C.POINTER(ViewerFrame), _P]),
 }
 
 
