@@ -8,6 +8,9 @@ as ``SkeletonWarp.forward`` + ``render(fused=True)``; what changes is the host: 
 become one and two (an eagerly issued frame at the bench workload is host-bound otherwise: bench.py ``eager_api``).  Frames the
 entry does not cover — the first frame of an arena (its size is not known yet), the MLP heads, top-K skinning, the optional
 branches of ``render`` — go through the separate calls, so the function can replace them unconditionally.
+
+What this node marshals like ``_PoseDeform`` (the PoseMLP's parameters, pointers and hand-off buffer, the two small-block layouts,
+the gradient split, the scalar motion mask, ``d_scaling``) is defined once, next to ``_PoseMLPFn`` in riggs_amd/skeleton.py.
 """
 from __future__ import annotations
 
@@ -19,7 +22,8 @@ import torch
 from . import _lib as L
 from .rasterizer import GaussianRasterizationSettings, RasterArena, _backward_workspace, _cfg, _LAST_WORKSPACE
 from .render import RenderPkg, _zero_points, render
-from .skeleton import _PoseMLPFn
+from .skeleton import (_PoseMLPFn, _mask_tensor, _pose_block, _pose_block_floats, _pose_grad_block, _pose_grad_block_floats,
+                       _split_grads, _zero_scaling)
 
 
 def _req(name, t, shape):
@@ -54,11 +58,7 @@ class _FrameFn(torch.autograd.Function):
         rho = _req("_node_radius", rho, (J,))
         mflat = None if mask is None else _req("motion_mask", mask.reshape(-1), (N,))
         joints, par = sw._joints(), sw._parents_dev(dev)
-        sync = pn._hip_sync
-        if sync.device != dev or sync.numel() * 4 < lib.riggs_pose_mlp_sync_bytes(depth, width):
-            sync = None
-        else:
-            pn.watch()
+        sync = pn.handoff(dev)
         keep = []
         cfg = _cfg(settings, N, f_dc.shape[1] + f_rest.shape[1], True, isotropic, keep, arena.tight_lists)
         # outputs and saved state: ONE float allocation for the per-joint arrays, the PoseMLP's activations, the residuals and
@@ -73,7 +73,7 @@ class _FrameFn(torch.autograd.Function):
                 _SIZES.clear()
             sizes = _SIZES[skey] = (lib.riggs_pose_mlp_acts_floats(depth, width, pn.multires), lib.riggs_raster_geom_bytes(N),
                                     lib.riggs_raster_image_bytes(H, W))
-        n_small, n_acts = J * 23 + 4, sizes[0]
+        n_small, n_acts = _pose_block_floats(J), sizes[0]
         o_acts = up(n_small)
         o_dx = o_acts + up(n_acts)
         o_dr = o_dx + up(3 * N)
@@ -81,8 +81,7 @@ class _FrameFn(torch.autograd.Function):
         o_rad = o_cnt + 64
         fbuf = torch.empty(o_rad + up(N), **f32)
         small, acts = fbuf[:n_small], fbuf[o_acts:o_acts + n_acts]
-        local_rot, transforms = small[:J * 4].view(J, 4), small[J * 4:J * 16].view(J, 12)
-        node_rot, d_nodes, global_trans = small[J * 16:J * 20].view(J, 4), small[J * 20:J * 23].view(J, 3), small[J * 23:J * 23 + 3]
+        local_rot, transforms, node_rot, d_nodes, global_trans = _pose_block(small, J)
         d_xyz, d_rot = fbuf[o_dx:o_dx + 3 * N].view(N, 3), fbuf[o_dr:o_dr + 4 * N].view(N, 4)
         ibuf = fbuf.view(torch.int32)
         counters, radii = ibuf[o_cnt:o_cnt + 4], ibuf[o_rad:o_rad + N]
@@ -93,12 +92,10 @@ class _FrameFn(torch.autograd.Function):
         color, depth_img, alpha = out[:3], out[3:4], out[4:5]
         arena.resolve(block=True)
         binning = arena.ensure(int(arena.last_R * arena.growth) + 1, N, H, W, dev)
-        Wp, bp = _PoseMLPFn._ptrs(params, depth)
-        h = params[2 * depth:]
         fr = L.Frame()
-        fr.depth, fr.width, fr.multires, fr.skip, fr.n_rot = depth, width, pn.multires, pn.skips[0], h[0].shape[0]
+        fr.depth, fr.width, fr.multires, fr.skip, fr.n_rot = depth, width, pn.multires, pn.skips[0], params[2 * depth].shape[0]
+        Wp, bp, fr.W_rot, fr.b_rot, fr.W_tr, fr.b_tr = _PoseMLPFn._ptrs(params, depth)
         fr.weights, fr.biases = C.cast(Wp, C.c_void_p), C.cast(bp, C.c_void_p)
-        fr.W_rot, fr.b_rot, fr.W_tr, fr.b_tr = h[0].data_ptr(), h[1].data_ptr(), h[2].data_ptr(), h[3].data_ptr()
         fr.t, fr.rot_bias4, fr.sync_state, fr.acts = t.data_ptr(), L.ptr(sw._rot_bias), L.ptr(sync), acts.data_ptr()
         fr.local_rot, fr.global_trans = local_rot.data_ptr(), global_trans.data_ptr()
         fr.num_joints, fr.K = J, sw.K
@@ -142,8 +139,7 @@ class _FrameFn(torch.autograd.Function):
         drho = grad_out(rho, (J,))
         need_mask = mflat is not None and ctx.needs_input_grad[2]
         dmask = torch.empty(N, **f32) if need_mask else None
-        small = torch.empty(J * 16 + 8, **f32)
-        dG, dq, dgt_s, dgt = small[:J * 12], small[J * 12:J * 16].view(J, 4), small[J * 16:J * 16 + 3], small[J * 16 + 4:J * 16 + 7]
+        dG, dq, dgt_s, dgt = _pose_grad_block(torch.empty(_pose_grad_block_floats(J), **f32), J)
         flat = grad_out_flat(params)
         ws = _backward_workspace(lib.riggs_raster_backward_workspace_bytes(N), dev, N)
         lws = torch.empty(lib.riggs_lbs_backward_workspace_bytes(N, J), dtype=torch.uint8, device=dev)
@@ -167,10 +163,8 @@ class _FrameFn(torch.autograd.Function):
             _WORKSPACES.clear()
             raise
         _LAST_WORKSPACE[:] = [ws, N]
-        # (one split + a view per matrix: a slice and a view per parameter were 30 us of an eager frame)
-        grads = [g_ if p.dim() == 1 else g_.view(p.shape) for g_, p in zip(flat.split_with_sizes([p.numel() for p in params]), params)]
         gmask = dmask.reshape(mask_shape) if need_mask else None
-        return (None, drho, gmask, g_xyz, g_m2d, g_dc, g_rest, g_op, g_sc, g_rot, None, *grads)
+        return (None, drho, gmask, g_xyz, g_m2d, g_dc, g_rest, g_op, g_sc, g_rot, None, *_split_grads(flat, params))
 
 
 def _covered(pc, sw, pipe, t, kw):
@@ -207,13 +201,6 @@ def deform_render(viewpoint_camera, pc, sw, pipe, bg_color, scaling_modifier=1.0
         for k in ("d_nodes", "local_rotation", "global_trans", "d_xyz", "d_rotation", "d_scaling"):
             dict.__setitem__(pkg, k, dv[k])
         return pkg
-    pn = sw.pose_net
-    params = []
-    for layer in pn.net._modules.values():  # (straight from the registries: Module.__getattr__ per access is 10 us a frame)
-        pd = layer._parameters
-        params += [pd["weight"], pd["bias"]]
-    for head in (pn._modules["rotation_predictor"], pn._modules["translation_predictor"]):
-        params += [head._parameters["weight"], head._parameters["bias"]]
     settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
@@ -222,16 +209,12 @@ def deform_render(viewpoint_camera, pc, sw, pipe, bg_color, scaling_modifier=1.0
         prefiltered=False, debug=pipe.debug)
     iso = bool(getattr(pc, "use_isotropic_gs", False))
     scaling = pc._scaling[..., :1] if iso else pc._scaling
-    mask = pc.motion_mask
-    if mask is not None and not isinstance(mask, torch.Tensor):
-        mask = None if float(mask) == 1.0 else torch.full((pc._xyz.shape[0], 1), float(mask), device=pc._xyz.device)
+    mask = _mask_tensor(pc.motion_mask, pc._xyz.shape[0], pc._xyz.device)
     pts = _zero_points(pc._xyz)
     color, radii, depth, alpha, d_nodes, local_rot, global_trans, d_xyz, d_rot = _FrameFn.apply(
         t[0].reshape(1), sw._node_radius, mask, pc._xyz, pts, pc._features_dc, pc._features_rest, pc._opacity, scaling,
-        pc._rotation, (sw, settings, arena, iso), *params)
-    zs = getattr(sw, "_zero_scaling", None)
-    if zs is None or zs.shape[0] != d_xyz.shape[0] or zs.device != d_xyz.device:
-        zs = sw._zero_scaling = torch.zeros(d_xyz.shape[0], 3, device=d_xyz.device)
+        pc._rotation, (sw, settings, arena, iso), *sw.pose_net.c_params())
     return RenderPkg({"render": color, "viewspace_points": pts, "visibility_filter": None, "radii": radii, "depth": depth,
                       "alpha": alpha, "bg_color": bg_color, "d_nodes": d_nodes, "local_rotation": local_rot,
-                      "global_trans": global_trans, "d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": zs})
+                      "global_trans": global_trans, "d_xyz": d_xyz, "d_rotation": d_rot,
+                      "d_scaling": _zero_scaling(sw, d_xyz.shape[0], d_xyz.device)})

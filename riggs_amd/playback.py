@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from .skeleton import _mask_tensor, _zero_scaling
 
 __all__ = ["slerp_batch", "run_interpolation", "get_geometric_color", "get_color_for_skinning_weights", "skinning_colors",
            "deform_sequence", "render_sequence", "sequence_pass_frames"]
@@ -173,9 +174,7 @@ def deform_sequence(sw, x, poses, motion_mask, _weight_mod=None):
         N, J = int(x.shape[0]), int(joints.shape[0])
         lr, gt, gt_stride = _track(poses, J, x.device)
         M = int(lr.shape[0])
-        mask = motion_mask
-        if mask is not None and not isinstance(mask, torch.Tensor):
-            mask = None if float(mask) == 1.0 else torch.full((N, 1), float(mask), device=x.device)
+        mask = _mask_tensor(motion_mask, N, x.device)
         mflat = None if mask is None else L.require_cuda_f32("motion_mask", mask.detach().reshape(-1), (N,))
         wm = _head_weight_mod(sw, x) if _weight_mod is None else _weight_mod
         f32 = dict(dtype=torch.float32, device=x.device)
@@ -192,9 +191,7 @@ def deform_sequence(sw, x, poses, motion_mask, _weight_mod=None):
                 off = sw._head_detail(x, lr[f].reshape(-1)[None].expand(N, -1))
                 d_xyz[f] += off if m3 is None else off * m3
         sw._emb_cache = None
-        zs = getattr(sw, "_zero_scaling", None)
-        if zs is None or zs.shape[0] != N or zs.device != x.device:
-            zs = sw._zero_scaling = torch.zeros(N, 3, device=x.device)
+        zs = _zero_scaling(sw, N, x.device)
     return {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": zs, "d_nodes": d_nodes, "local_rotation": lr, "global_trans": gt}
 
 

@@ -104,23 +104,33 @@ class PoseMLP(nn.Module):
                 and self.net[0].in_features == 1 + 2 * self.multires and len(self.net) <= 12
                 and all(l.out_features == w for l in self.net))
 
+    def c_params(self):
+        """The parameters in the order every C entry takes them (_PoseMLPFn._ptrs): ``weight, bias`` per layer, then the rotation
+        head's, then the translation head's.  Straight from the registries: Module.__getattr__ per access is 10 us a frame."""
+        params = []
+        for layer in self._modules["net"]._modules.values():
+            pd = layer._parameters
+            params += [pd["weight"], pd["bias"]]
+        for head in (self._modules["rotation_predictor"], self._modules["translation_predictor"]):
+            params += [head._parameters["weight"], head._parameters["bias"]]
+        return params
+
+    def handoff(self, device):
+        """The persistent hand-off state for a launch on ``device`` — after a look at its status word (``watch``) — or None,
+        when it lives elsewhere or is too small for this library: the library then clears a private state per call."""
+        sync = self._buffers["_hip_sync"]
+        net = self._modules["net"]
+        if sync.device != device or sync.numel() * 4 < L.lib().riggs_pose_mlp_sync_bytes(len(net), net[0].out_features):
+            return None
+        self.watch()
+        return sync
+
     def forward(self, t, rot_bias=None):
         """``rot_bias`` (4,) is added to every predicted quaternion (skeleton_warp.py:118 does it outside the
         network; folding it into the head kernel saves one elementwise launch per frame)."""
         if self._fusable(t):  # one row: three HIP launches instead of ~60 torch ops
-            params = []
-            for l in self.net:
-                params += [l.weight, l.bias]
-            params += [self.rotation_predictor.weight, self.rotation_predictor.bias,
-                       self.translation_predictor.weight, self.translation_predictor.bias]
-            sync = self._hip_sync
-            if sync.device != t.device or sync.numel() * 4 < L.lib().riggs_pose_mlp_sync_bytes(len(self.net),
-                                                                                                   self.net[0].out_features):
-                sync = None  # the library then clears a private state per call
-            else:
-                self.watch()
             rot, tr = _PoseMLPFn.apply(t.reshape(1), len(self.net), self.net[0].out_features, self.multires,
-                                       self.skips[0], rot_bias, sync, *params)
+                                       self.skips[0], rot_bias, self.handoff(t.device), *self.c_params())
             return {"rotation": rot, "translation": tr}
         t_emb = _embed(t, self.multires) if self.multires > 0 else t
         h = t_emb + 0.0
@@ -207,10 +217,13 @@ class _PoseMLPFn(torch.autograd.Function):
 
     @staticmethod
     def _ptrs(params, depth):
+        """``PoseMLP.c_params()`` as the six arguments of the C entries: the per-layer weight and bias pointer arrays (the caller
+        keeps them alive while a struct points at them), then W_rot, b_rot, W_tr, b_tr."""
         import ctypes as C
         Wp = (C.c_void_p * depth)(*[params[2 * l].data_ptr() for l in range(depth)])
         bp = (C.c_void_p * depth)(*[params[2 * l + 1].data_ptr() for l in range(depth)])
-        return Wp, bp
+        return (Wp, bp, params[2 * depth].data_ptr(), params[2 * depth + 1].data_ptr(), params[2 * depth + 2].data_ptr(),
+                params[2 * depth + 3].data_ptr())
 
     @staticmethod
     def forward(ctx, t, depth, width, multires, skip, rot_bias, sync, *params):
@@ -222,10 +235,7 @@ class _PoseMLPFn(torch.autograd.Function):
         acts = torch.empty(lib.riggs_pose_mlp_acts_floats(depth, width, multires), dtype=torch.float32, device=dev)
         rot = torch.empty(n_rot, dtype=torch.float32, device=dev)
         tr = torch.empty(3, dtype=torch.float32, device=dev)
-        Wp, bp = _PoseMLPFn._ptrs(params, depth)
-        h = params[2 * depth:]
-        L.check(lib.riggs_pose_mlp_forward(depth, width, multires, skip, n_rot, Wp, bp, h[0].data_ptr(),
-                                           h[1].data_ptr(), h[2].data_ptr(), h[3].data_ptr(), t.data_ptr(),
+        L.check(lib.riggs_pose_mlp_forward(depth, width, multires, skip, n_rot, *_PoseMLPFn._ptrs(params, depth), t.data_ptr(),
                                            L.ptr(rot_bias), L.ptr(sync), acts.data_ptr(), rot.data_ptr(), tr.data_ptr(), L.stream_ptr()),
                 "riggs_pose_mlp_forward")
         ctx.save_for_backward(acts, *params)
@@ -243,20 +253,54 @@ class _PoseMLPFn(torch.autograd.Function):
         g_tr = torch.zeros(3, device=dev) if g_tr is None else g_tr.contiguous()
         from .dist import grad_out_flat
         flat = grad_out_flat(params)  # the flat gradient bucket's own range when one is registered
-        dzs = torch.empty(lib.riggs_pose_mlp_backward_workspace_floats(depth, width, multires), dtype=torch.float32,
-                          device=dev)
-        Wp, bp = _PoseMLPFn._ptrs(params, depth)
-        h = params[2 * depth:]
-        L.check(lib.riggs_pose_mlp_backward(depth, width, multires, skip, n_rot, Wp, bp, h[0].data_ptr(),
-                                            h[1].data_ptr(), h[2].data_ptr(), h[3].data_ptr(), acts.data_ptr(),
+        dzs = torch.empty(lib.riggs_pose_mlp_backward_workspace_floats(depth, width, multires), dtype=torch.float32, device=dev)
+        L.check(lib.riggs_pose_mlp_backward(depth, width, multires, skip, n_rot, *_PoseMLPFn._ptrs(params, depth), acts.data_ptr(),
                                             g_rot.data_ptr(), g_tr.data_ptr(), dzs.data_ptr(), flat.data_ptr(),
                                             L.ptr(ctx.sync), L.stream_ptr()), "riggs_pose_mlp_backward")
-        grads, o = [], 0
-        for p in params:
-            n = p.numel()
-            grads.append(flat[o:o + n].view_as(p))
-            o += n
-        return (None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, *_split_grads(flat, params))
+
+
+def _split_grads(flat, params):
+    """The flat PoseMLP gradient as one view per parameter (one split + a view per matrix: a slice and a view per parameter
+    were 30 us of an eagerly issued frame)."""
+    return [g if p.dim() == 1 else g.view(p.shape) for g, p in zip(flat.split_with_sizes([p.numel() for p in params]), params)]
+
+
+def _pose_block_floats(J):
+    return 23 * J + 4
+
+
+def _pose_block(flat, J):
+    """The per-joint arrays of one pose in ONE float allocation (_PoseDeform, riggs_amd.frame._FrameFn): ``flat`` -> local_rot
+    (J, 4), transforms (J, 12), node_rot (J, 4) — each on a 16-byte boundary of the block —, d_nodes (J, 3), global_trans (3,)."""
+    return (flat[:4 * J].view(J, 4), flat[4 * J:16 * J].view(J, 12), flat[16 * J:20 * J].view(J, 4), flat[20 * J:23 * J].view(J, 3),
+            flat[23 * J:23 * J + 3])
+
+
+def _pose_grad_block_floats(J):
+    return 16 * J + 8
+
+
+def _pose_grad_block(flat, J):
+    """The backward's small gradients, likewise: ``flat`` -> dG (J, 12), dq (J, 4), dgt (3,): the skinning's part of
+    dL/dglobal_trans, dgt_total (3,): all of it."""
+    return flat[:12 * J].view(J, 12), flat[12 * J:16 * J].view(J, 4), flat[16 * J:16 * J + 3], flat[16 * J + 4:16 * J + 7]
+
+
+def _mask_tensor(mask, N, device):
+    """The motion mask as the nodes take it: None (also for the scalar 1.0: no mask), a tensor as it is, any other scalar as an
+    (N, 1) tensor."""
+    if mask is None or isinstance(mask, torch.Tensor):
+        return mask
+    return None if float(mask) == 1.0 else torch.full((N, 1), float(mask), device=device)
+
+
+def _zero_scaling(sw, N, device):
+    """``d_scaling``: a constant zero (N, 3) (skeleton_warp.py:165), kept on the module between calls."""
+    zs = getattr(sw, "_zero_scaling", None)
+    if zs is None or zs.shape[0] != N or zs.device != device:
+        zs = sw._zero_scaling = torch.zeros(N, 3, device=device)
+    return zs
 
 
 # --------------------------------------------------------------------------- HIP ops
@@ -325,34 +369,41 @@ class _DeformByPose(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_xyz, g_rot, g_nodes, g_transforms, _g_node_rot):
         local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod = ctx.saved_tensors
-        N, J = x.shape[0], joints.shape[0]
+        J = joints.shape[0]
         f32 = dict(dtype=torch.float32, device=x.device)
-        g_xyz = torch.zeros(N, 3, **f32) if g_xyz is None else g_xyz.contiguous()
-        g_rot = torch.zeros(N, 4, **f32) if g_rot is None else g_rot.contiguous()
-        dG = torch.empty(J, 12, **f32)
-        from .dist import grad_out
-        drho = grad_out(rho, (J,))
-        dgt = torch.empty(3, **f32)
-        need_mask = mflat is not None and ctx.needs_input_grad[3]
-        dmask = torch.empty(N, **f32) if need_mask else None
-        dmod = torch.empty(N, J - 1, **f32) if weight_mod is not None else None
-        lib = L.lib()
-        st = L.stream_ptr()
-        ws = torch.empty(lib.riggs_lbs_backward_workspace_bytes(N, J), dtype=torch.uint8, device=x.device)
-        L.check(lib.riggs_lbs_backward(N, J, ctx.K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(),
-                                       rho.data_ptr(), transforms.data_ptr(), node_rot.data_ptr(),
-                                       global_trans.data_ptr(), L.ptr(mflat), L.ptr(weight_mod), g_xyz.data_ptr(),
-                                       g_rot.data_ptr(), dG.data_ptr(), drho.data_ptr(), dgt.data_ptr(), L.ptr(dmask),
-                                       L.ptr(dmod), ws.data_ptr(), st),
-                "riggs_lbs_backward")
-        if g_transforms is not None:
-            dG = dG + g_transforms
+        dG, dgt = torch.empty(J, 12, **f32), torch.empty(3, **f32)
+        dG, drho, dmask, dmod = _skinning_backward(ctx.K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat,
+                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[3])
         dq = torch.empty(J, 4, **f32)
         gn = None if g_nodes is None else g_nodes.contiguous()
-        L.check(lib.riggs_fk_backward(J, local_rot.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), dG.data_ptr(),
-                                      L.ptr(gn), dq.data_ptr(), dgt.data_ptr(), st), "riggs_fk_backward")
-        gmask = dmask.reshape(ctx.mask_shape) if need_mask else None
+        L.check(L.lib().riggs_fk_backward(J, local_rot.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), dG.data_ptr(),
+                                          L.ptr(gn), dq.data_ptr(), dgt.data_ptr(), L.stream_ptr()), "riggs_fk_backward")
+        gmask = None if dmask is None else dmask.reshape(ctx.mask_shape)
         return dq, dgt, drho, gmask, None, None, None, None, dmod
+
+
+def _skinning_backward(K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat, weight_mod, g_xyz, g_rot,
+                       g_transforms, dG, dgt, want_mask):
+    """riggs_lbs_backward for _DeformByPose and _PoseDeform: fills the caller's ``dG`` (J, 12) and ``dgt`` (3,); returns
+    (dG + g_transforms where the returned transforms have a cotangent, drho — the gradient bucket's own range when one is
+    registered —, dmask (N,) or None, dmod (N, J - 1) or None).  A missing cotangent of d_xyz / d_rotation counts as zeros."""
+    N, J = x.shape[0], joints.shape[0]
+    f32 = dict(dtype=torch.float32, device=x.device)
+    g_xyz = torch.zeros(N, 3, **f32) if g_xyz is None else g_xyz.contiguous()
+    g_rot = torch.zeros(N, 4, **f32) if g_rot is None else g_rot.contiguous()
+    from .dist import grad_out
+    drho = grad_out(rho, (J,))
+    dmask = torch.empty(N, **f32) if mflat is not None and want_mask else None
+    dmod = torch.empty(N, J - 1, **f32) if weight_mod is not None else None
+    lib = L.lib()
+    ws = torch.empty(lib.riggs_lbs_backward_workspace_bytes(N, J), dtype=torch.uint8, device=x.device)
+    L.check(lib.riggs_lbs_backward(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
+                                   transforms.data_ptr(), node_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat),
+                                   L.ptr(weight_mod), g_xyz.data_ptr(), g_rot.data_ptr(), dG.data_ptr(), drho.data_ptr(),
+                                   dgt.data_ptr(), L.ptr(dmask), L.ptr(dmod), ws.data_ptr(), L.stream_ptr()), "riggs_lbs_backward")
+    if g_transforms is not None:
+        dG = dG + g_transforms
+    return dG, drho, dmask, dmod
 
 
 _ACTS_FLOATS = {}  # PoseMLP shape -> riggs_pose_mlp_acts_floats
@@ -384,20 +435,16 @@ class _PoseDeform(torch.autograd.Function):
         if n_acts is None:
             n_acts = _ACTS_FLOATS[key] = lib.riggs_pose_mlp_acts_floats(depth, width, multires)
         o_small = (n_acts + 63) & ~63
-        sbuf = torch.empty(o_small + J * 23 + 4, **f32)
-        acts, small = sbuf[:n_acts], sbuf[o_small:]
-        local_rot, transforms = small[:J * 4].view(J, 4), small[J * 4:J * 16].view(J, 12)
-        node_rot, d_nodes, global_trans = small[J * 16:J * 20].view(J, 4), small[J * 20:J * 23].view(J, 3), small[J * 23:J * 23 + 3]
+        sbuf = torch.empty(o_small + _pose_block_floats(J), **f32)
+        acts = sbuf[:n_acts]
+        local_rot, transforms, node_rot, d_nodes, global_trans = _pose_block(sbuf[o_small:], J)
         o_rot = (3 * N + 63) & ~63
         dbuf = torch.empty(o_rot + 4 * N, **f32)
         d_xyz, d_rot = dbuf[:3 * N].view(N, 3), dbuf[o_rot:].view(N, 4)
-        Wp, bp = _PoseMLPFn._ptrs(params, depth)
-        h = params[2 * depth:]
         st = L.stream_ptr()
-        L.check(lib.riggs_pose_mlp_forward(depth, width, multires, skip, n_rot, Wp, bp, h[0].data_ptr(), h[1].data_ptr(),
-                                           h[2].data_ptr(), h[3].data_ptr(), t.data_ptr(), L.ptr(rot_bias), L.ptr(sync),
-                                           acts.data_ptr(), local_rot.data_ptr(), global_trans.data_ptr(), st),
-                "riggs_pose_mlp_forward")
+        L.check(lib.riggs_pose_mlp_forward(depth, width, multires, skip, n_rot, *_PoseMLPFn._ptrs(params, depth), t.data_ptr(),
+                                           L.ptr(rot_bias), L.ptr(sync), acts.data_ptr(), local_rot.data_ptr(),
+                                           global_trans.data_ptr(), st), "riggs_pose_mlp_forward")
         L.check(lib.riggs_lbs_forward_fk(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
                                          local_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat), L.ptr(weight_mod),
                                          transforms.data_ptr(), node_rot.data_ptr(), d_nodes.data_ptr(), d_xyz.data_ptr(),
@@ -414,45 +461,28 @@ class _PoseDeform(torch.autograd.Function):
     def backward(ctx, g_xyz, g_rot, g_nodes, g_local_rot, g_global_trans, g_transforms, _g_node_rot):
         acts, local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod, *params = ctx.saved_tensors
         depth, width, multires, skip, n_rot, K = ctx.cfg
-        N, J = x.shape[0], joints.shape[0]
-        lib, dev = L.lib(), x.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        g_xyz = torch.zeros(N, 3, **f32) if g_xyz is None else g_xyz.contiguous()
-        g_rot = torch.zeros(N, 4, **f32) if g_rot is None else g_rot.contiguous()
-        bsmall = torch.empty(J * 16 + 12, **f32)  # (dG | dq | dgt | dgt_total: one allocation)
-        dG, dq = bsmall[:J * 12].view(J, 12), bsmall[J * 12:J * 16].view(J, 4)
-        dgt, dgt_total = bsmall[J * 16:J * 16 + 3], bsmall[J * 16 + 4:J * 16 + 7]
-        from .dist import grad_out, grad_out_flat
-        drho = grad_out(rho, (J,))
-        need_mask = mflat is not None and ctx.needs_input_grad[4]
-        dmask = torch.empty(N, **f32) if need_mask else None
-        dmod = torch.empty(N, J - 1, **f32) if weight_mod is not None else None
-        st = L.stream_ptr()
-        ws = torch.empty(lib.riggs_lbs_backward_workspace_bytes(N, J), dtype=torch.uint8, device=dev)
-        L.check(lib.riggs_lbs_backward(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
-                                       transforms.data_ptr(), node_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat),
-                                       L.ptr(weight_mod), g_xyz.data_ptr(), g_rot.data_ptr(), dG.data_ptr(), drho.data_ptr(),
-                                       dgt.data_ptr(), L.ptr(dmask), L.ptr(dmod), ws.data_ptr(), st), "riggs_lbs_backward")
-        if g_transforms is not None:
-            dG = dG + g_transforms
+        lib, J = L.lib(), joints.shape[0]
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dG, dq, dgt, dgt_total = _pose_grad_block(torch.empty(_pose_grad_block_floats(J), **f32), J)  # (one allocation)
+        dG, drho, dmask, dmod = _skinning_backward(K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat,
+                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[4])
         if g_global_trans is not None:
             dgt = dgt + g_global_trans.reshape(-1)
         gn = None if g_nodes is None else g_nodes.contiguous()
         gq = None if g_local_rot is None else g_local_rot.contiguous()
+        from .dist import grad_out_flat
         flat = grad_out_flat(params)  # the flat gradient bucket's own range when one is registered
         dzs = torch.empty(lib.riggs_pose_mlp_backward_workspace_floats(depth, width, multires), **f32)
-        Wp, bp = _PoseMLPFn._ptrs(params, depth)
-        h = params[2 * depth:]
-        L.check(lib.riggs_pose_mlp_backward_fk(depth, width, multires, skip, n_rot, Wp, bp, h[0].data_ptr(), h[1].data_ptr(),
-                                               h[2].data_ptr(), h[3].data_ptr(), acts.data_ptr(), J, local_rot.data_ptr(),
-                                               joints.data_ptr(), parents_i32.data_ptr(), transforms.data_ptr(), dG.data_ptr(), L.ptr(gn), L.ptr(gq),
+        L.check(lib.riggs_pose_mlp_backward_fk(depth, width, multires, skip, n_rot, *_PoseMLPFn._ptrs(params, depth), acts.data_ptr(),
+                                               J, local_rot.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(),
+                                               transforms.data_ptr(), dG.data_ptr(), L.ptr(gn), L.ptr(gq),
                                                dgt.data_ptr(), dq.data_ptr(), dgt_total.data_ptr(),
                                                L.ptr(ctx.fixed[0]) if ctx.fixed else None, L.ptr(ctx.fixed[1]) if ctx.fixed else None,
-                                               dzs.data_ptr(), flat.data_ptr(), L.ptr(ctx.sync), st), "riggs_pose_mlp_backward_fk")
-        # (one split + a view per matrix: a slice and a view per parameter were 30 us of an eagerly issued frame)
-        grads = [g_ if p.dim() == 1 else g_.view(p.shape) for g_, p in zip(flat.split_with_sizes([p.numel() for p in params]), params)]
-        gmask = dmask.reshape(ctx.mask_shape) if need_mask else None
-        return (None, None, None, drho, gmask, None, None, None, None, dmod, None, None, None, None, None, *grads)
+                                               dzs.data_ptr(), flat.data_ptr(), L.ptr(ctx.sync), L.stream_ptr()),
+                "riggs_pose_mlp_backward_fk")
+        gmask = None if dmask is None else dmask.reshape(ctx.mask_shape)
+        return (None, None, None, drho, gmask, None, None, None, None, dmod, None, None, None, None, None,
+                *_split_grads(flat, params))
 
 
 class _LazyDeformDict(dict):
@@ -742,9 +772,7 @@ class SkeletonWarp(NodeGaussians, nn.Module):
             local_rot, global_trans = node_attrs["local_rotation"], node_attrs["global_trans"]
         joints = self._joints()
         par = self._parents_dev(x.device)
-        mask = motion_mask
-        if mask is not None and not isinstance(mask, torch.Tensor):
-            mask = None if float(mask) == 1.0 else torch.full((x.shape[0], 1), float(mask), device=x.device)
+        mask = _mask_tensor(motion_mask, x.shape[0], x.device)
         weight_mod = None
         if self.use_skinning_weight_mlp:  # skeleton_warp.py:56-61
             if self.K > 0:
@@ -755,16 +783,7 @@ class SkeletonWarp(NodeGaussians, nn.Module):
             self.skinning_weight_offsets = weight_mod
         if _time is not None:
             pn = self.pose_net
-            params = []
-            for l in pn.net:
-                params += [l.weight, l.bias]
-            params += [pn.rotation_predictor.weight, pn.rotation_predictor.bias, pn.translation_predictor.weight,
-                       pn.translation_predictor.bias]
-            sync = pn._hip_sync
-            if sync.device != x.device or sync.numel() * 4 < L.lib().riggs_pose_mlp_sync_bytes(len(pn.net), pn.net[0].out_features):
-                sync = None
-            else:
-                pn.watch()
+            params, sync = pn.c_params(), pn.handoff(x.device)
             self._fixed_folded = getattr(self, "template_fixed", None) is not None
             from . import _torch_ext as TX
             from .dist import _SLICES, _entry
@@ -806,11 +825,8 @@ class SkeletonWarp(NodeGaussians, nn.Module):
             _, _, w, idx = lbs_forward(x, joints, par, rho.contiguous(), transforms.detach(), node_rot, gt, mflat,
                                        self.K, want_weights=True, weight_mod=wm)
             return w, idx
-        zs = getattr(self, "_zero_scaling", None)
-        if zs is None or zs.shape[0] != x.shape[0] or zs.device != x.device:
-            zs = self._zero_scaling = torch.zeros(x.shape[0], 3, device=x.device)  # constant (skeleton_warp.py:165)
         return _LazyDeformDict(
-            {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": zs,
+            {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": _zero_scaling(self, x.shape[0], x.device),
              "d_nodes": d_nodes, "nn_idx": None, "nn_weight": None, "local_rotation": node_attrs["local_rotation"],
              "global_trans": global_trans, "d_opacity": None, "d_color": None}, producer=producer)
 
