@@ -22,6 +22,11 @@ extern "C" {
 
 typedef void* riggs_stream; /* hipStream_t */
 
+/* The ABI version.  It is bumped when the signature of an EXISTING function or the layout of an EXISTING struct changes; added
+ * symbols and enumerators appended to an enum do not bump it (the ABI grows: a caller that needs a new symbol resolves it by
+ * name).  riggs_version() returns the value the library was built with; a consumer compiled against this header compares that
+ * with its own RIGGS_ABI_VERSION and refuses the library when they differ (riggs_amd/_lib.py, csrc_torch/riggs_torch.cpp). */
+#define RIGGS_ABI_VERSION 101
 int riggs_version(void);
 const char* riggs_last_error(void);
 
@@ -234,7 +239,7 @@ size_t riggs_raster_backward_workspace_bytes_ordered(int32_t num_points, int64_t
  * counters != NULL: when the frame's overflow flag (counters[1]) is set the forward writes a ZERO image and the backward ZERO
  * gradients, decided on the device (as riggs_raster_backward); NULL skips the guard.  num_points == 0 is valid: the image is bg.
  * Neither call allocates, reads back or synchronises (cfg.debug: synchronises and checks): both are legal inside a stream capture.
- * (Added symbols do not change riggs_version(): the ABI only grows; a caller that needs them resolves them by name.) */
+ * (Added symbols: RIGGS_ABI_VERSION is unchanged.) */
 int riggs_raster_recolor_forward(const riggs_raster_cfg* cfg /* N, H, W */, const void* geom, const void* binning,
                                  int64_t instance_capacity, const void* image_state, const uint32_t* counters /* NULL: no guard */,
                                  const float* colors /*(N,3)*/, const float* bg /*(3,)*/, float* out_color /*(3,H,W)*/,
@@ -308,8 +313,8 @@ int riggs_lbs_backward(int32_t num_points, int32_t num_joints, int32_t K, const 
                        void* workspace /* riggs_lbs_backward_workspace_bytes(N, J) */, riggs_stream stream);
 size_t riggs_lbs_backward_workspace_bytes(int32_t num_points, int32_t num_joints);
 
-/* ---- Playback of a pose track (inference only: no backward exists; riggs_amd/playback.py).  Added symbols: riggs_version() is
- * what it was.
+/* ---- Playback of a pose track (inference only: no backward exists; riggs_amd/playback.py).  Added symbols: RIGGS_ABI_VERSION
+ * is unchanged.
  * riggs_lbs_sequence_forward: M poses over ONE canonical cloud.  A launch in front runs the kinematic chain of every frame
  * (one wave per frame up to 64 joints, one 256-thread workgroup beyond) and writes transforms (M,J,12), node_rot (M,J,4),
  * d_nodes (M,J,3); the skinning launch keeps one Gaussian per thread — position, top-K set, weight_mod row: once — and walks
@@ -1042,7 +1047,7 @@ int riggs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float*
 /* =====================================================================
  * The editor's display frame (riggs_amd/viewer.py): interactive_GUI.py::test_step :497-664 with its overlay builders :97-247,
  * render_rig.py::project_nodes_to_2d_withnodes :40-94 and utils/other_utils.py::depth2normal :78-97.  Inference only; every
- * launch goes on `stream`, nothing synchronises.  Added symbols: riggs_version() is unchanged.
+ * launch goes on `stream`, nothing synchronises.  Added symbols: RIGGS_ABI_VERSION is unchanged.
  *
  * A PRIMITIVE is RIGGS_VIEWER_PRIM_WORDS = 12 32-bit words: [0] kind (segment / disc / axis-aligned square), [1..4] the integer
  * end points x0 y0 x1 y1 (a disc's centre twice; a square's left_top and right_bottom), [5] the DOUBLED extent of the colour

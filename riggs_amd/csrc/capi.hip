@@ -129,7 +129,7 @@ static int defer_lookup(const void* geom) {  // -1: unknown (the arena of a fram
   return -1;
 }
 
-int riggs_version(void) { return 100; }
+int riggs_version(void) { return RIGGS_ABI_VERSION; }
 
 int riggs_prof_count(void) { return PROF_COUNT; }
 const char* riggs_prof_name(int32_t id) { return (id >= 0 && id < PROF_COUNT) ? kProfNames[id] : ""; }

@@ -303,7 +303,8 @@ std::vector<Tensor> glue_raster(const Tensor& xyz, const Tensor& means2D, const 
                              workspace, cap, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, debug, isotropic, tight_lists);
 }
 
-int64_t abi_version() { return (int64_t)riggs_version(); }
+// (the header THIS file was compiled against, not a call into whatever libriggs_hip.so is loaded: _torch_ext.available() compares)
+int64_t abi_version() { return (int64_t)RIGGS_ABI_VERSION; }
 
 }  // namespace
 

@@ -23,13 +23,19 @@ import torch
 from . import _lib as L
 from .playback import get_geometric_color
 
-PRIM_WORDS = 12
-SEGMENT, DISC, SQUARE = 0, 1, 2
-RULE_EDITOR, RULE_RENDER_RIG = 0, 1
-LAYOUT_SKELETON, LAYOUT_SQUARES, LAYOUT_POLYLINES = 0, 1, 2
-BLEND_ALPHA, BLEND_MASK = 0, 1
-MODES = {"render": 0, "skinning": 0, "depth": 1, "alpha": 2, "normal_dep": 3}
-MAX_TABLES = 8
+
+def _viewer(*names):
+    """The header's RIGGS_VIEWER_* values of these names."""
+    return [L.CONSTANTS["RIGGS_VIEWER_" + n] for n in names]
+
+
+PRIM_WORDS, MAX_TABLES, RANGE_WORKSPACE_FLOATS = _viewer("PRIM_WORDS", "MAX_TABLES", "RANGE_WORKSPACE_FLOATS")
+SEGMENT, DISC, SQUARE = _viewer("SEGMENT", "DISC", "SQUARE")
+RULE_EDITOR, RULE_RENDER_RIG = _viewer("RULE_EDITOR", "RULE_RENDER_RIG")
+LAYOUT_SKELETON, LAYOUT_SQUARES, LAYOUT_POLYLINES = _viewer("LAYOUT_SKELETON", "LAYOUT_SQUARES", "LAYOUT_POLYLINES")
+BLEND_ALPHA, BLEND_MASK = _viewer("BLEND_ALPHA", "BLEND_MASK")
+MODE_IMAGE, MODE_DEPTH, MODE_ALPHA, MODE_NORMAL = _viewer("MODE_IMAGE", "MODE_DEPTH", "MODE_ALPHA", "MODE_NORMAL")
+MODES = {"render": MODE_IMAGE, "skinning": MODE_IMAGE, "depth": MODE_DEPTH, "alpha": MODE_ALPHA, "normal_dep": MODE_NORMAL}
 EDGE_COLOR = (68 / 255, 114 / 255, 196 / 255)            # :173
 REFERENCE_EDGE_COLOR = (237 / 255, 125 / 255, 49 / 255)  # :240
 
@@ -203,11 +209,11 @@ def depth_range(depth):
     """``(2,)`` = [min, max] of a depth map on the device: bit-identical to ``torch.min`` / ``torch.max``, without their two
     reductions' launches and with no atomics."""
     depth = L.require_cuda_f32("depth", depth.detach())
-    ws = torch.empty(512 + 2, dtype=torch.float32, device=depth.device)
+    ws = torch.empty(RANGE_WORKSPACE_FLOATS + 2, dtype=torch.float32, device=depth.device)
     with torch.cuda.device(depth.device):
-        L.check(L.lib().riggs_viewer_depth_range(depth.numel(), depth.data_ptr(), ws.data_ptr(), ws[512:].data_ptr(), L.stream_ptr()),
-                "riggs_viewer_depth_range")
-    return ws[512:]
+        L.check(L.lib().riggs_viewer_depth_range(depth.numel(), depth.data_ptr(), ws.data_ptr(), ws[RANGE_WORKSPACE_FLOATS:].data_ptr(),
+                                                 L.stream_ptr()), "riggs_viewer_depth_range")
+    return ws[RANGE_WORKSPACE_FLOATS:]
 
 
 def _depth_hw(depth):
@@ -307,6 +313,6 @@ def draw_skeleton_on_image(camera, nodes, parents, rgba_image, thickness=1):
                      disc_color_ext2=6, disc_alpha_ext2=6)[0]
     white = black.clone()
     white[:, 7:10] = 0x3f800000  # (the bits of 1.0f)
-    rgb = _compose(0, img[:3], (H, W), [black], [BLEND_ALPHA])
-    a = _compose(2, img[3], (H, W), [white], [BLEND_ALPHA])
+    rgb = _compose(MODE_IMAGE, img[:3], (H, W), [black], [BLEND_ALPHA])
+    a = _compose(MODE_ALPHA, img[3], (H, W), [white], [BLEND_ALPHA])
     return torch.cat([rgb.permute(2, 0, 1), a.permute(2, 0, 1)[:1]], dim=0)

@@ -231,18 +231,13 @@ def test_the_control_point_mask_rule():
 def test_header_declares_every_viewer_symbol_the_binding_has():
     from riggs_amd import _lib as L
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "riggs_hip.h")).read(), flags=re.S)
-    bound = sorted(k for k in L._SIGS if k.startswith("riggs_viewer_"))
-    assert bound == sorted(SYMBOLS)
-    for name in SYMBOLS:
-        m = re.search(r"\bint(?:32_t|64_t)?\s+%s\s*\(([^;]*)\)\s*;" % name, txt)
-        assert m, name + " is not declared in include/riggs_hip.h"
-        assert len(L._SIGS[name][1]) == len(m.group(1).split(",")), name + ": argument count"
+    # (the binding is read from the header; tests/test_capi_cpu.py has the compiler check every signature and layout)
+    assert sorted(k for k in L.exported_symbols() if k.startswith("riggs_viewer_")) == sorted(SYMBOLS)
     for struct, cls in (("riggs_viewer_projection", L.ViewerProjection), ("riggs_viewer_frame", L.ViewerFrame)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), txt, flags=re.S).group(1)
         names = [re.sub(r"\[.*?\]", "", n).strip(" *") for decl in body.split(";") if decl.strip()
                  for n in re.sub(r"^\s*(const\s+)?\w+\s*\*?\s*", "", decl.strip(), count=1).split(",")]
         assert names == [f[0] for f in cls._fields_], struct
-    assert re.search(r"\bint\s+riggs_version\s*\(\s*void\s*\)", txt)
     assert "viewer.hip" in __import__("riggs_amd.build", fromlist=["SOURCES"]).SOURCES
 
 
