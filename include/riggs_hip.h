@@ -1129,6 +1129,33 @@ typedef struct riggs_viewer_frame {
 } riggs_viewer_frame;
 int riggs_viewer_compose(const riggs_viewer_frame* f, riggs_stream stream);
 
+/* =====================================================================
+ * 2-D skeleton thinning of silhouette masks (csrc/thin.hip; riggs_amd/thinning.py): what process_data/cal_2d_skeleton.py makes
+ * offline with skimage.morphology.thin and scene/dataset_readers.py reads back as viewpoint_cam.thinned.  Guo and Hall's
+ * two-subiteration parallel thinning, restated from the published algorithm (the conditions are spelled out in csrc/thin.hip);
+ * it reproduces the published 7 x 7 example of skimage's documentation, agreement with an installed skimage beyond that is not
+ * verified.  Integer only; images are bytes, set = non-zero on input and 1 on output.  Added symbols: RIGGS_ABI_VERSION is
+ * unchanged.
+ *
+ * Sub-iteration number n (from 0) applies table (first_subiter + n) % 2; after every second one an image stops if the pair
+ * deleted nothing.  max_subiters < 0: until converged; otherwise exactly at most that many sub-iterations run.
+ * PATH LDS: one workgroup per image keeps the bit plane in LDS, one launch for the batch, nothing synchronises.  PATH GLOBAL
+ * (images whose plane does not fit): one launch per sub-iteration over planes in `workspace`
+ * (riggs_thin_workspace_bytes(B, H, W, path) bytes, 256-byte aligned; 0 for the LDS path), and every check_every iterations the
+ * host reads back the per-image deletion counters: this path synchronises `stream` and cannot be captured.  PATH AUTO takes
+ * riggs_thin_path(H, W) (-1 for sizes outside 1 .. 32768).
+ * ===================================================================== */
+enum { RIGGS_THIN_PATH_AUTO = -1, RIGGS_THIN_PATH_LDS = 0, RIGGS_THIN_PATH_GLOBAL = 1 };
+int32_t riggs_thin_path(int32_t H, int32_t W);
+size_t riggs_thin_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t path);
+int riggs_thin(int32_t B, int32_t H, int32_t W, const uint8_t* mask_u8, uint8_t* out_u8, int32_t first_subiter,
+               int32_t max_subiters, int32_t path, int32_t check_every, void* workspace, riggs_stream stream);
+/* The set (non-zero) pixels of B images (H, W) of bytes as float32 rows (row, col), each coordinate
+ * (float)((double)v / resolution), in row-major ascending order (np.where's), one workgroup per image: points (B, capacity, 2),
+ * counts (B) int32 = min(number of set pixels, capacity).  Rows at and beyond counts[b] are not written. */
+int riggs_thin_elements(int32_t B, int32_t H, int32_t W, const uint8_t* img_u8, double resolution, int32_t capacity, float* points,
+                        int32_t* counts, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

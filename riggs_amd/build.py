@@ -44,6 +44,7 @@ SOURCES = {
     # which is what its tests compare with — no CPU oracle has to be matched bit for bit here.
     "metrics.hip": ["-ffp-contract=fast"],
     "viewer.hip": ["-ffp-contract=off"],  # (the display frame's base colour in the reference's own steps; its coverage is integer)
+    "thin.hip": ["-ffp-contract=off"],  # (integer but for the coordinates' one float64 division: nothing to contract)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",
