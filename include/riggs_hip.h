@@ -1156,6 +1156,46 @@ int riggs_thin(int32_t B, int32_t H, int32_t W, const uint8_t* mask_u8, uint8_t*
 int riggs_thin_elements(int32_t B, int32_t H, int32_t W, const uint8_t* img_u8, double resolution, int32_t capacity, float* points,
                         int32_t* counts, riggs_stream stream);
 
+/* =====================================================================
+ * Multiresolution hash-grid encoding (csrc/hashgrid.hip; riggs_amd/hash_network.py): the encoding of the reference's
+ * HashDeformNetwork (utils/time_utils.py:517-571, 712-767), which it takes from tinycudann.Encoding ("Grid" / "Hash" / "Linear").
+ * Restated from the published algorithm (Mueller et al., Instant Neural Graphics Primitives, 2022; tests/hashgrid_ref.py is the
+ * NumPy restatement); tinycudann does not build for this platform, so agreement with its binary is NOT verified: checkpoint
+ * exchange rests on the layout below and on the published algorithm.  Added symbols: RIGGS_ABI_VERSION is unchanged.
+ *
+ * D = n_input_dims in {3, 4}, L = n_levels in 1 .. 16, F = n_features_per_level = 2, log2_hashmap_size in 3 .. 24, linear
+ * interpolation.  All integer arithmetic is uint32 with wrap-around.  Per level l:
+ *   scale[l] = (float)(base_resolution * pow(per_level_scale, l) - 1)       (in double, rounded once)
+ *   resolution[l] = ceil(scale[l]) + 1
+ *   size[l] = min(round_up_8(resolution[l]^D), 2^log2_hashmap_size)          (the power exact, in 64 bits)
+ *   hashed[l] = resolution[l]^D > size[l]   (0: a dense level);   offset[l] = size[0] + .. + size[l-1], offset[L] = the total
+ * The table is (offset[L], F) fp32: level-major, entry-major, feature-minor.
+ * Per row and level: pos_d = fmaf(scale, x_d, 0.5f), cell_d = (uint32)(int32)floorf(pos_d), frac_d = pos_d - floorf(pos_d); over
+ * the 2^D corners c = cell + bit the weight is prod_d (bit_d ? frac_d : 1 - frac_d) and the entry is
+ *   dense:  (sum_d c_d * resolution^d) % size        hashed:  (xor_d c_d * prime_d) % size,  primes {1, 2654435761, 805459861, 3674653429}
+ * so every index is in range for any finite coordinate, also outside [0, 1] (taken as it comes, no clamp; |pos| < 2^31).
+ * out (R, L F), column l F + f.  mask: L F floats or NULL; it multiplies the output in the forward and the cotangent in the
+ * backward; a level whose two mask values are 0 is not gathered (its columns are 0) and not scattered.
+ * backward ADDS w * mask * g_out[row][l F + f] into g_table (same layout as the table; the caller zeroes it) with float atomic
+ * adds: the sum's order is the arrival order, so the table gradient can differ in its last bits from run to run.  The
+ * coordinates are not differentiated.  x, table, out, g_out, g_table are device pointers, 8-byte aligned; 0 <= R < 2^31 / (L F).
+ * Neither call allocates, reads back or synchronises.  riggs_hashgrid_levels_fill is host arithmetic only (no HIP call).
+ * ===================================================================== */
+#define RIGGS_HASHGRID_MAX_LEVELS 16
+/* The per-level table is RIGGS_HASHGRID_TABLE_WORDS 32-bit words in HOST memory: [0] n_input_dims, [1] n_levels,
+ * [2] n_features_per_level, [3] log2_hashmap_size, [4] the entries of the whole table (offset[L]), [5..7] 0, then
+ * RIGGS_HASHGRID_LEVEL_WORDS words per level l at RIGGS_HASHGRID_HEADER_WORDS + 5 l: the bits of the float scale[l],
+ * resolution[l], size[l], offset[l], hashed[l]. */
+#define RIGGS_HASHGRID_HEADER_WORDS 8
+#define RIGGS_HASHGRID_LEVEL_WORDS 5
+#define RIGGS_HASHGRID_TABLE_WORDS 88
+int riggs_hashgrid_levels_fill(int32_t n_input_dims, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
+                               double base_resolution, double per_level_scale, uint32_t* levels /* host, TABLE_WORDS words */);
+int riggs_hashgrid_forward(const uint32_t* levels /* host */, int32_t R, const float* x /*(R,D)*/, const float* table,
+                           const float* mask /* or NULL */, float* out /*(R,L F)*/, riggs_stream stream);
+int riggs_hashgrid_backward(const uint32_t* levels /* host */, int32_t R, const float* x /*(R,D)*/, const float* mask /* or NULL */,
+                            const float* g_out /*(R,L F)*/, float* g_table, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

@@ -10,7 +10,8 @@ kernel's neighbour lists) and ``skinning=True`` (softmax of a per-Gaussian (N, M
 path, time_utils.py:1165-1213: an as-rigid-as-possible re-posing of the Gaussians around dragged nodes, under ``no_grad``) in
 torch ops on top of the kernel's blend — it runs per mouse event, not per training step.  The node network
 (``self.network``: nodes, t -> per-node attributes; 512-1024 rows, time_utils.py:990-1002) is a torch module supplied by the
-caller: ``riggs_amd.node_network.DeformNetwork`` (csrc/node_mlp.hip) for the shipped flags, or any module ``(x, t) -> dict``.
+caller: ``riggs_amd.node_network.DeformNetwork`` (csrc/node_mlp.hip) for the shipped flags, ``riggs_amd.hash_network.HashDeformNetwork``
+(csrc/hashgrid.hip) with ``use_hash=True``, or any module ``(x, t) -> dict``.
 No CPU / eager fallback.
 """
 from __future__ import annotations
@@ -215,8 +216,9 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
                  pred_opacity=False, pred_color=False, skinning=False, is_blender=False, init_pcl=None, use_hash=False,
                  hash_time=False, enable_densify_prune=False, with_arap_loss=False, is_scene_static=False, **kwargs):
         super().__init__()
-        if use_hash:
-            raise NotImplementedError("use_hash: the hash-grid node network needs tinycudann, which is not part of this library")
+        if use_hash and not (network is not None and "bbox" in dict(network.named_buffers())):
+            raise NotImplementedError("use_hash: this constructor builds no network itself — pass network=HashDeformNetwork(...) "
+                                      "(riggs_amd.hash_network), or any module with a 'bbox' buffer")
         if skinning and local_frame:
             raise NotImplementedError("skinning with local_frame: the reference's own forward fails there (its einsum expects per-"
                                       "Gaussian neighbour lists, time_utils.py:1152)")
@@ -289,6 +291,8 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
             return
         self.inited.data = torch.ones_like(self.inited)
         dev = init_pcl.device
+        if self.use_hash and reset_bbox and hasattr(self.network, "bbox"):  # the hash grid's box (time_utils.py:895-896), no read-back
+            self.network.bbox.data = torch.stack([init_pcl.min() - .1, init_pcl.max() + .1]).float().to(self.network.bbox.device)
         if keep_all or self.node_num > init_pcl.shape[0]:
             self.nodes = nn.Parameter(torch.cat([init_pcl.float(), 1e-2 * torch.ones(init_pcl.shape[0], self.hyper_dim, device=dev)], -1))
             init_nodes_idx = None
