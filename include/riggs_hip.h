@@ -1196,6 +1196,36 @@ int riggs_hashgrid_forward(const uint32_t* levels /* host */, int32_t R, const f
 int riggs_hashgrid_backward(const uint32_t* levels /* host */, int32_t R, const float* x /*(R,D)*/, const float* mask /* or NULL */,
                             const float* g_out /*(R,L F)*/, float* g_table, riggs_stream stream);
 
+/* =====================================================================
+ * A semantic label per control node (csrc/semantic.hip; riggs_amd/skeleton_init.py: node_semantic_labels), the input of the
+ * skeleton extraction's symmetry pass.  Replaces, for all F training frames in one launch, what the trainer does camera by camera:
+ *   TrainRig.init_skeleton_info / set_semantic_label   train_rig.py:129-131, 177-190, 215-216
+ *   torch.median(nodes_semantic_label, dim=0).values.int()   train_rig.py:227
+ * d_nodes (F, M, 3): the nodes at every frame; cameras: a DEVICE table of F records, record f the camera of frame f.
+ * Per (f, m): (row, col) = (fy y / z + cy, fx x / z + cx) of the node in camera space, the projection of
+ * riggs_node_projection_forward in the same fp32 steps (project_nodes_to_2d_elements, utils/other_utils.py:101-127); both
+ * truncated toward zero; row >= H -> H - 1 and col >= W -> W - 1, THEN whatever is < 0 -> 0; labels[f][m] = map[row][col].
+ * A record whose map is NULL (a camera without semantic_seg) gives 0 for its whole row f.  A projection that is not finite
+ * (z = 0, a NaN node) is undefined in the reference; here it reads pixel (0, 0).
+ * Outputs: labels (F, M) fp32, the reference's nodes_semantic_label; median (M,) int32, per node the LOWER median of its F
+ * labels — the element of rank (F - 1) / 2, torch.median's rule — taken over the fp32 values and converted back, as the
+ * reference does (exact for |label| <= 2^24).
+ * 1 <= F <= RIGGS_SEMANTIC_MAX_FRAMES, 1 <= M <= RIGGS_SEMANTIC_MAX_NODES, else an error and no launch.  One launch of
+ * ceil(M / T) workgroups of 256 threads with 4 F T <= 65536 bytes of LDS, T = riggs_node_semantic_tile(F) nodes per workgroup
+ * (0 for an F out of range).  Does not allocate, read back or synchronise: legal inside a stream capture.  The maps (and the
+ * table) must stay alive until the launch has run.  Added symbols: RIGGS_ABI_VERSION is unchanged.
+ * ===================================================================== */
+#define RIGGS_SEMANTIC_MAX_FRAMES 1024
+#define RIGGS_SEMANTIC_MAX_NODES 65536
+/* A camera record is RIGGS_SEMANTIC_CAMERA_WORDS 32-bit words (8-byte aligned): [0 .. 15] the floats of world_view_transform,
+ * (4, 4) row-major as the reference stores it (row-vector convention); [16 .. 19] the floats fx, fy, cx, cy; [20], [21] int32
+ * image_height H and image_width W, the shape of the map (1 <= H, W < 2^24; a record with H < 1 or W < 1 is read as one without
+ * a map); [22 .. 23] the 64-bit device pointer to the (H, W) int32 map, or 0. */
+#define RIGGS_SEMANTIC_CAMERA_WORDS 24
+int32_t riggs_node_semantic_tile(int32_t F);
+int riggs_node_semantic_labels(int32_t F, int32_t M, const float* d_nodes, const void* cameras /* device: F records */,
+                               float* labels, int32_t* median, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

@@ -14,6 +14,7 @@
 // only atomics are 64-bit max and integer adds.  Sizes are tiny (P ≈ 0.5-3 k points, M ≈ 0.1-5 k pixels): the work is
 // launch-bound, so the bone form is kept to four kernel nodes of a captured iteration.
 #include "common.h"
+#include "pinhole.h"
 
 namespace riggs {
 
@@ -52,15 +53,12 @@ __device__ __forceinline__ void skel_point(const SkelProjArgs& a, int p, float& 
   } else {
     px = a.nodes[3 * p + 0]; py = a.nodes[3 * p + 1]; pz = a.nodes[3 * p + 2];
   }
-  const float* V = a.view;
-  tx = px * V[0] + py * V[4] + pz * V[8] + V[12];
-  ty = px * V[1] + py * V[5] + pz * V[9] + V[13];
-  tz = px * V[2] + py * V[6] + pz * V[10] + V[14];
+  pinhole_view(a.view, px, py, pz, tx, ty, tz);
 }
 
 // the pinhole: (row, col) of a camera-space point
 __device__ __forceinline__ float2 skel_pinhole(const SkelProjArgs& a, float tx, float ty, float tz) {
-  return make_float2(a.fy * ty / tz + a.cy, a.fx * tx / tz + a.cx);
+  return pinhole_row_col(a.fx, a.fy, a.cx, a.cy, tx, ty, tz);
 }
 
 template <bool BONES>

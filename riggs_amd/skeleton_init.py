@@ -8,8 +8,11 @@ of at most 200 vertices: host code over numpy, written from the algorithm each s
 behaviour where that behaviour looks accidental (each such point is named where it happens) — a skeleton extracted here is the
 skeleton the reference extracts from the same trajectories.
 
-The symmetry pass (``apply_symmetry``, extract_skeleton_utils.py:177-255) needs per-camera semantic maps that one dataset has:
-``seg_labels`` other than None raises NotImplementedError.
+The symmetry pass (``apply_symmetry``, extract_skeleton_utils.py:177-255) runs when ``obtain_skeleton_tree`` is given a label per
+node together with ``symmetry=True`` (opt-in: nothing a caller does today changes its tree).  The reference's trainer always
+gives one: the median over the training frames of the label each node projects onto in the frame's semantic map, and zero for a camera without a map (train_rig.py:129-131, 177-190, 227) — so all zeros for a dataset without
+maps, which is not the same as no labels.  ``node_semantic_labels`` computes labels and median for all frames in one launch
+(csrc/semantic.hip); ``precompute_deformations(..., cameras=, symmetry=True)`` is the trainer's call.
 """
 from __future__ import annotations
 
@@ -220,12 +223,80 @@ def _split_path(path, pts, dist_thres, num_thres=3):
     return pieces
 
 
-def simplify_tree(all_points, parents, dist_thres=1.0):
+# ---- the symmetry pass (extract_skeleton_utils.py:165-255 compute_single_source_path_distance, apply_symmetry) ------------
+def compute_single_source_path_distance(all_points, path):
+    """(len(path),) arc length along ``path`` from its first vertex, each edge the mean over the frames of its length (:165-173).
+    A trailing -1 (a chain that ran past the root) reads the last vertex."""
+    pts = np.asarray(all_points, dtype=np.float64)
+    path = np.asarray(path, dtype=np.int64)
+    edge = np.linalg.norm(pts[:, path[:-1]] - pts[:, path[1:]], axis=-1).mean(0)
+    return np.concatenate([[0.0], np.cumsum(edge)])
+
+
+def apply_symmetry(paths, edge_idxs, all_points, semantic_label, length_thres=0.7, semantic_thres=0.6):
+    """Chains that look like each other's mirror image get the same cut (:177-255).  ``paths``: the chains of ``simplify_tree``,
+    each with its trailing parent entry; ``edge_idxs``: per chain its pieces as pairs of positions in it; ``semantic_label`` (n,)
+    integers per vertex.  Chains are paired greedily — chain i with the later chain j of the best score
+    ``length_ratio + semantic_score`` among those with ``length_ratio = 1 - |len_i - len_j| / max(len_i, len_j) > length_thres``
+    and ``semantic_score = |labels_i & labels_j| / max(|labels_i|, |labels_j|) > semantic_thres`` (label SETS) — and in each pair
+    the pieces of the chain whose piece count is nearer 2 are carried over to the other chain by normalised arc length.
+    Returns ``edge_idxs`` (the same list, the carried-over entries replaced); nothing changes when no pair qualifies.
+    Kept from the reference although it looks accidental: see the comments."""
+    label = np.asarray(semantic_label)
+    # the labels of a chain INCLUDE its trailing parent entry; where that is -1 (past the root) it reads the LAST label
+    sets = [np.unique(label[np.asarray(p, dtype=np.int64)]) for p in paths]
+    pairs = []
+    taken = np.zeros(len(paths), dtype=bool)
+    for i in range(len(paths)):
+        if taken[i]:  # (only as the first of a pair: a taken chain may still be chosen as j by a later i)
+            continue
+        best_score, best = 0, -1
+        for j in range(i + 1, len(paths)):
+            len_i, len_j = len(paths[i]), len(paths[j])
+            if len(edge_idxs[i]) == 1 and len(edge_idxs[j]) == 1:  # skipped only when BOTH chains are one piece
+                continue
+            length_ratio = 1.0 - abs(len_i - len_j) / (max(len_i, len_j) + 1e-10)
+            if length_ratio > length_thres:
+                semantic_score = len(np.intersect1d(sets[i], sets[j])) / (max(len(sets[i]), len(sets[j])) + 1e-10)
+                if semantic_score > semantic_thres:
+                    score = length_ratio + semantic_score
+                    if score > best_score:  # strictly: the first best wins
+                        best_score, best = score, j
+        if best >= 0:
+            pairs.append((i, best))
+            taken[best] = True
+    for first, second in pairs:
+        # the chain whose piece count is nearer 2 gives its cut to the other; on equality that is the SECOND of the pair
+        if abs(len(edge_idxs[first]) - 2) < abs(len(edge_idxs[second]) - 2):
+            select, other = first, second
+        else:
+            select, other = second, first
+        pieces = sorted(edge_idxs[select], key=lambda e: e[0])
+        d_select = compute_single_source_path_distance(all_points, paths[select])
+        d_other = compute_single_source_path_distance(all_points, paths[other])
+        d_select, d_other = d_select / d_select[-1], d_other / d_other[-1]  # normalised by the last entry (the whole chain)
+        carried = []
+        for k in range(len(pieces)):
+            start = 0 if k == 0 else int(np.argmin(np.abs(d_select[pieces[k][0]] - d_other)))
+            # the reference compares the PIECE counter with the chain's LENGTH (a chain of n entries has at most n - 1 pieces, so
+            # this never holds) and would then take a vertex ID, paths[other][-1], where a position in the chain is meant;
+            # simplify_tree raises IndexError where such an entry does not index the chain, as the reference does
+            if k == len(paths[select]) - 1:
+                end = int(paths[other][-1])
+            else:
+                end = int(np.argmin(np.abs(d_select[pieces[k][1]] - d_other)))
+            carried.append((start, end))
+        edge_idxs[other] = carried
+    return edge_idxs
+
+
+def simplify_tree(all_points, parents, semantic_label=None, dist_thres=1.0):
     """Every chain between two key vertices (leaf or junction below, junction or root above) is cut into straight pieces; the
     ends of the pieces stay, with the upper end of its piece as parent, everything else becomes -2.  The threshold is
     ``dist_thres`` mean edge lengths of the tree (:307-316).  Vertex 0 is made the root whatever the pieces say (:300).
     A chain that runs past the root ends in "vertex -1", read as the last vertex like everywhere in Python.
-    ``all_points`` (F, n, 3): the vertices' trajectories; distances are taken in float64."""
+    ``all_points`` (F, n, 3): the vertices' trajectories; distances are taken in float64.  ``semantic_label`` (n,) integers, or
+    None: with labels the pieces of all chains go through ``apply_symmetry`` before they are written (:294-295)."""
     pts = np.asarray(all_points, dtype=np.float64)
     parents = np.asarray(parents, dtype=np.int64)
     n = len(parents)
@@ -236,7 +307,7 @@ def simplify_tree(all_points, parents, dist_thres=1.0):
     is_key = np.array([len(c) > 1 for c in children])
     has = parents >= 0
     mean_edge = np.linalg.norm(pts[:, parents[has]] - pts[:, has], axis=-1).mean(0).mean()
-    new_parents = np.full(n, -2, dtype=np.int64)
+    paths, edge_idxs = [], []
     for v in range(n):
         p = int(parents[v])
         if p < 0 or not (len(children[v]) == 0 or is_key[v]):
@@ -247,7 +318,19 @@ def simplify_tree(all_points, parents, dist_thres=1.0):
             if p < 0 or is_key[p]:
                 break
             p = int(parents[p])
-        for a, b in _split_path(path, pts, dist_thres * mean_edge):
+        paths.append(path)
+        edge_idxs.append(_split_path(path, pts, dist_thres * mean_edge))
+    if semantic_label is not None:
+        semantic_label = np.asarray(semantic_label).reshape(-1)
+        if semantic_label.shape[0] != n:
+            raise ValueError("simplify_tree: %d labels for %d vertices" % (semantic_label.shape[0], n))
+        edge_idxs = apply_symmetry(paths, edge_idxs, pts, semantic_label)
+    new_parents = np.full(n, -2, dtype=np.int64)
+    for path, pieces in zip(paths, edge_idxs):
+        for a, b in pieces:
+            if not (-len(path) <= a < len(path) and -len(path) <= b < len(path)):
+                raise IndexError("simplify_tree: the symmetry pass carried the piece (%d, %d) over to a chain of %d entries — "
+                                 "apply_symmetry took a vertex id for a position in the chain, as the reference does" % (a, b, len(path)))
             new_parents[path[a]] = path[b]
     new_parents[0] = -1
     return new_parents
@@ -259,11 +342,12 @@ def mean_pairwise_distances(points):
     return torch.norm(points.unsqueeze(-2) - points.unsqueeze(-2).transpose(1, 2), dim=-1).mean(dim=0)
 
 
-def tree_from_samples(select_nodes, sample_indices, mean_distances, all_deformed_nodes):
+def tree_from_samples(select_nodes, sample_indices, mean_distances, all_deformed_nodes, seg_labels=None):
     """The host stages of ``obtain_skeleton_tree`` (:450-471) on numpy arrays — the sampled nodes (S, 3), their indices (S,), the
     (S, S) mean distances and all nodes' trajectories (F, M, 3): a dict of every stage's result (``prim``, ``order1`` /
     ``parents1`` / ``indices1`` of the first re-rooting, ``pruned``, ``simplified``) and the final ``joints`` (fp32),
-    ``parents`` (int64), ``indices`` (int32)."""
+    ``parents`` (int64), ``indices`` (int32).  ``seg_labels`` (M,) integers per node, or None: the symmetry pass of
+    ``simplify_tree``, which reads them by the re-rooted tree's node indices (:459)."""
     select_nodes = np.asarray(select_nodes, dtype=np.float32)
     sample_indices = np.asarray(sample_indices)
     traj = np.asarray(all_deformed_nodes)
@@ -271,24 +355,37 @@ def tree_from_samples(select_nodes, sample_indices, mean_distances, all_deformed
     order1, parents1 = reroot(prim)
     nodes1, indices1 = select_nodes[order1], sample_indices[order1]
     pruned, nodes1 = prune_tree(nodes1, parents1)
-    simplified = simplify_tree(traj[:, indices1], pruned)
+    simplified = simplify_tree(traj[:, indices1], pruned, None if seg_labels is None else np.asarray(seg_labels).reshape(-1)[indices1])
     order2, parents2 = reroot(simplified)
     return {"prim": prim, "order1": order1, "parents1": parents1, "indices1": indices1.astype(np.int32), "pruned": pruned,
             "simplified": simplified, "joints": nodes1[order2], "parents": parents2, "indices": indices1[order2].astype(np.int32)}
 
 
-def obtain_skeleton_tree(nodes, all_deformed_nodes, seg_labels=None, start=None):
+def obtain_skeleton_tree(nodes, all_deformed_nodes, seg_labels=None, start=None, symmetry=False):
     """The sparse skeleton of the control nodes (extract_skeleton_utils.py:426-471).  ``nodes`` (M, 3): the nodes at the template
     frame; ``all_deformed_nodes`` (F, M, 3): at every training frame.  Returns ``(joints (J, 3) fp32, parents (J,) int64 with
     -1 at joint 0, indices (J,) int32)`` on the nodes' device; ``indices[j]`` is the node joint j came from.  More than 200 nodes
-    are sampled down to 200 by farthest points from a random start (``start``: that index, for a reproducible run)."""
-    if seg_labels is not None:
-        raise NotImplementedError("seg_labels: the symmetry pass over semantic labels (apply_symmetry) is not part of this "
-                                  "library — it needs per-camera semantic maps; pass seg_labels=None")
+    are sampled down to 200 by farthest points from a random start (``start``: that index, for a reproducible run).
+    ``seg_labels`` with ``symmetry=True``: an (M,) integer tensor on any device — a semantic label per node
+    (``node_semantic_labels``'s median, or zeros: what the reference's trainer passes); the chains of the tree then go through
+    the symmetry pass (``apply_symmetry``).  An all-zero vector is NOT the same as None: every pair of chains then matches
+    semantically.  The pass is opt-in: labels without ``symmetry=True`` raise NotImplementedError, as they always have — a caller
+    written before the pass existed does not silently get another tree — and ``symmetry=True`` needs labels."""
+    if seg_labels is not None and not symmetry:
+        raise NotImplementedError("seg_labels: the symmetry pass over semantic labels (apply_symmetry) is opt-in — pass "
+                                  "symmetry=True with the labels to run it, or seg_labels=None for the tree without it")
+    if symmetry and seg_labels is None:
+        raise ValueError("symmetry=True needs seg_labels: a label per node (zeros are what the reference passes without maps)")
     from .gaussian_model import farthest_point_sample
     dev = nodes.device
     nodes, all_deformed_nodes = nodes.detach(), all_deformed_nodes.detach()
     M = nodes.shape[0]
+    if seg_labels is not None:
+        seg_labels = torch.as_tensor(seg_labels).detach()
+        if seg_labels.is_floating_point() or seg_labels.is_complex() or seg_labels.dtype is torch.bool or seg_labels.numel() != M:
+            raise ValueError("seg_labels must be an integer tensor of one label per node (%d), got %s %s"
+                             % (M, tuple(seg_labels.shape), seg_labels.dtype))
+        seg_labels = seg_labels.reshape(-1).cpu().numpy()
     if M > SAMPLE_NODES:
         st = None if start is None else torch.as_tensor(start, dtype=torch.long).reshape(1)
         sample = farthest_point_sample(nodes.float().unsqueeze(0), SAMPLE_NODES, start=st)[0]
@@ -296,9 +393,66 @@ def obtain_skeleton_tree(nodes, all_deformed_nodes, seg_labels=None, start=None)
         sample = torch.arange(M, device=dev)
     mean_distances = mean_pairwise_distances(all_deformed_nodes[:, sample])
     out = tree_from_samples(nodes[sample].float().cpu().numpy(), sample.cpu().numpy(), mean_distances.cpu().numpy(),
-                            all_deformed_nodes.float().cpu().numpy())
+                            all_deformed_nodes.float().cpu().numpy(), seg_labels)
     return (torch.from_numpy(out["joints"]).to(dev), torch.from_numpy(out["parents"]).to(dev),
             torch.from_numpy(out["indices"]).to(dev))
+
+
+# ---- the nodes' semantic labels (train_rig.py:129-131, 177-190, 215-216, 227) on csrc/semantic.hip ------------------------
+@torch.no_grad()
+def node_semantic_labels(d_nodes, cameras):
+    """A semantic label per control node from the training cameras' semantic maps, all frames in one launch
+    (``riggs_node_semantic_labels``): node m at frame f is projected into camera f as ``project_nodes_to_2d_elements`` does, the
+    pixel truncated and clamped into the image as ``set_semantic_label`` does, and the camera's map read there.
+
+    ``d_nodes`` (F, M, 3) fp32 on the device; ``cameras``: F objects in the order of ``d_nodes``' first axis, with
+    ``world_view_transform``, ``FoVx``, ``FoVy``, ``image_height``, ``image_width``, optionally ``K`` and optionally
+    ``semantic_seg`` — an (H, W) integer tensor (moved to the device and cast to int32 as needed) or None: such a camera's row
+    is all zero.  Returns ``(labels (F, M) fp32, median (M,) int32)`` on the device: the reference's ``nodes_semantic_label``
+    and its ``torch.median(dim=0).values.int()`` (the lower median), what ``obtain_skeleton_tree`` takes as ``seg_labels``.
+    1 <= F <= 1024, 1 <= M <= 65536."""
+    from . import _lib as L
+    from .loss import camera_intrinsics
+    if not isinstance(d_nodes, torch.Tensor) or d_nodes.dim() != 3 or d_nodes.shape[2] != 3:
+        raise L.RiggsHipError("node_semantic_labels: d_nodes must be (F, M, 3)")
+    d_nodes = L.require_cuda_f32("d_nodes", d_nodes.detach())
+    F, M = int(d_nodes.shape[0]), int(d_nodes.shape[1])
+    cameras = list(cameras)
+    if len(cameras) != F:
+        raise L.RiggsHipError("node_semantic_labels: %d cameras for %d frames of d_nodes" % (len(cameras), F))
+    if not (1 <= F <= L.CONSTANTS["RIGGS_SEMANTIC_MAX_FRAMES"] and 1 <= M <= L.CONSTANTS["RIGGS_SEMANTIC_MAX_NODES"]):
+        raise L.RiggsHipError("node_semantic_labels: needs 1 <= F <= %d frames and 1 <= M <= %d nodes, got F = %d, M = %d"
+                              % (L.CONSTANTS["RIGGS_SEMANTIC_MAX_FRAMES"], L.CONSTANTS["RIGGS_SEMANTIC_MAX_NODES"], F, M))
+    dev = d_nodes.device
+    words = L.CONSTANTS["RIGGS_SEMANTIC_CAMERA_WORDS"]  # the record of include/riggs_hip.h: 16 + 4 floats, H, W, the map's pointer
+    views = torch.stack([torch.as_tensor(c.world_view_transform).detach().to(device=dev, dtype=torch.float32).reshape(4, 4)
+                         for c in cameras]).cpu().numpy()
+    table = np.zeros((F, words), dtype=np.uint32)
+    maps = []  # (alive until the launch is enqueued: the caching allocator then keeps their memory for the stream)
+    for f, cam in enumerate(cameras):
+        H, W = int(cam.image_height), int(cam.image_width)
+        if not (1 <= H < 2 ** 24 and 1 <= W < 2 ** 24):
+            raise L.RiggsHipError("node_semantic_labels: camera %d: image of %d x %d" % (f, H, W))
+        table[f, :16] = views[f].reshape(16).view(np.uint32)
+        table[f, 16:20] = np.array(camera_intrinsics(cam), dtype=np.float32).view(np.uint32)
+        table[f, 20:22] = (H, W)
+        seg = getattr(cam, "semantic_seg", None)
+        if seg is None:
+            continue
+        seg = torch.as_tensor(seg).detach()
+        if tuple(seg.shape) != (H, W) or seg.is_floating_point() or seg.is_complex() or seg.dtype is torch.bool:
+            raise L.RiggsHipError("node_semantic_labels: camera %d: semantic_seg must be an integer (%d, %d) map, got %s %s"
+                                  % (f, H, W, tuple(seg.shape), seg.dtype))
+        seg = seg.to(device=dev, dtype=torch.int32).contiguous()
+        maps.append(seg)
+        table[f, 22:24] = (seg.data_ptr() & 0xFFFFFFFF, seg.data_ptr() >> 32)
+    table_dev = torch.from_numpy(table.view(np.int32)).to(dev)
+    labels = torch.empty(F, M, dtype=torch.float32, device=dev)
+    median = torch.empty(M, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().riggs_node_semantic_labels(F, M, d_nodes.data_ptr(), table_dev.data_ptr(), labels.data_ptr(), median.data_ptr(), L.stream_ptr()), "riggs_node_semantic_labels")
+    del maps
+    return labels, median
 
 
 def select_key_frame(d_nodes, coverage=None, manually_key_frame=-1):
@@ -336,7 +490,8 @@ def load_skeleton_tree(path, device="cpu"):
 
 # ---- train_rig.py:192-262 and the tail of init_skeleton_info (:135-141) --------------------------------------------------
 @torch.no_grad()
-def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=None, num_gs_sample=0, manually_key_frame=-1):
+def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=None, num_gs_sample=0, manually_key_frame=-1,
+                            cameras=None, symmetry=False):
     """The trained stage 1 at every training frame, and the skeleton drawn from it.  ``deform``: a ``ControlNodeWarp`` (or a
     model holding one as ``.deform``); ``gaussians``: the stage-1 ``GaussianModel``; ``fids`` (F,): the training frames' times,
     visited in ascending order (``coverage`` (F,), the frames' mask areas, is given in the order of ``fids``).
@@ -346,7 +501,14 @@ def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=N
     ``parent_indices``, ``joint_node_indices``, ``template_idx`` (an index into the sorted frames).  As in the reference the
     template frame becomes the rest pose: its ``d_xyz`` — the template offsets — is ADDED to ``gaussians._xyz`` and subtracted
     from every frame's ``d_xyz``.  ``num_gs_sample > 10`` first thins the Gaussians (``sampling_and_prune``); ``model_path``:
-    where ``skeleton_tree.npz`` and ``skeleton.obj`` are written."""
+    where ``skeleton_tree.npz`` and ``skeleton.obj`` are written.
+
+    ``symmetry=True`` is the reference trainer's call (train_rig.py:226-231): ``obtain_skeleton_tree`` gets a label per node and
+    runs the symmetry pass — with ``cameras`` (F objects in the order of ``fids``, see ``node_semantic_labels``) the median over
+    the frames of the labels the nodes project onto, ``node_semantic_labels(d_nodes, cameras)[1]``, and ``nodes_semantic_label``
+    (F, M) is returned in the first dict; without cameras an all-zero vector, what the reference passes for a dataset without
+    semantic maps (which still pairs chains, by length alone).  The default ``symmetry=False`` passes None — no symmetry pass,
+    which the reference's trainer never does; ``cameras`` alone changes nothing."""
     from .skeleton import write_to_obj
     warp = getattr(deform, "deform", deform)
     if num_gs_sample > 10:
@@ -357,6 +519,11 @@ def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=N
     fids = fids[order].to(dev)
     if coverage is not None:
         coverage = torch.as_tensor(coverage).reshape(-1).cpu()[order]
+    if cameras is not None:
+        cameras = list(cameras)
+        if len(cameras) != fids.shape[0]:
+            raise ValueError("precompute_deformations: %d cameras for %d frames" % (len(cameras), fids.shape[0]))
+        cameras = [cameras[int(i)] for i in order]
     xyz = gaussians.get_xyz.detach()
     stacks = {"d_xyz": [], "d_nodes": [], "d_rotation": [], "d_scaling": []}
     for i in range(fids.shape[0]):
@@ -365,7 +532,13 @@ def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=N
             stacks[k].append(d[k].detach())
     info = {k: torch.stack(v) for k, v in stacks.items()}
     template_idx = select_key_frame(info["d_nodes"], coverage, manually_key_frame)
-    joints, parent_indices, joint_node_indices = obtain_skeleton_tree(info["d_nodes"][template_idx], info["d_nodes"], None)
+    seg_labels = None
+    if symmetry and cameras is not None:
+        info["nodes_semantic_label"], seg_labels = node_semantic_labels(info["d_nodes"], cameras)
+    elif symmetry:
+        seg_labels = torch.zeros(info["d_nodes"].shape[1], dtype=torch.int32, device=dev)
+    joints, parent_indices, joint_node_indices = obtain_skeleton_tree(info["d_nodes"][template_idx], info["d_nodes"], seg_labels,
+                                                                      symmetry=seg_labels is not None)
     tree = {"joints": joints, "parent_indices": parent_indices, "joint_node_indices": joint_node_indices, "template_idx": int(template_idx)}
     if model_path is not None:
         os.makedirs(model_path, exist_ok=True)
