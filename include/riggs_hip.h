@@ -24,7 +24,8 @@ typedef void* riggs_stream; /* hipStream_t */
 
 /* The ABI version.  It is bumped when the signature of an EXISTING function or the layout of an EXISTING struct changes; added
  * symbols and enumerators appended to an enum do not bump it (the ABI grows: a caller that needs a new symbol resolves it by
- * name).  riggs_version() returns the value the library was built with; a consumer compiled against this header compares that
+ * name; nor does a REMOVED symbol or option name: a consumer that still names it fails at symbol resolution, or with "unknown
+ * option").  riggs_version() returns the value the library was built with; a consumer compiled against this header compares that
  * with its own RIGGS_ABI_VERSION and refuses the library when they differ (riggs_amd/_lib.py, csrc_torch/riggs_torch.cpp). */
 #define RIGGS_ABI_VERSION 101
 int riggs_version(void);
@@ -41,7 +42,6 @@ const char* riggs_last_error(void);
  *                             and of tiles, 0 = the direct counting sort, 1 = the two-level sort (identical lists, bit for bit).
  *                             riggs_raster_binning_bytes reserves the larger of the two layouts, so flipping this never
  *                             invalidates an arena
- *   "cnode_bwd_atomics" 0     1 = riggs_cnode_backward's first design (LDS float atomics); set it BEFORE sizing its workspace
  *   "color_side_jobs"   1     the SH colours of a frame are evaluated by extra workgroups of the tile sort's scatter launch
  *                             (riggs_raster_render) wherever the direct tile sort runs, instead of by riggs_raster_preprocess's
  *                             kernel: the same colours and clamp bits, bit for bit; the geometry arena's colours are then
@@ -695,9 +695,8 @@ int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, c
  * backward takes upstream gradients (each may be NULL = 0) and writes the gradients of feature (N, feat_stride; columns
  * beyond `hyper` zero), motion_mask, the node attributes, _node_radius, _node_weight and the nodes' hyper coordinates
  * (M, hyper); xyz of Gaussians and nodes are detached in the reference (:944, :947-949, :1152).  workspace:
- * riggs_cnode_backward_workspace_floats floats, 16-byte aligned.
+ * riggs_cnode_backward_workspace_floats = 33 N K + max(1, ceil(N K / 4096)) M + M + 1 + 8 floats, 16-byte aligned; M <= 4096.
  * ===================================================================== */
-int riggs_cnode_backward_blocks(int32_t N, int32_t M, int32_t hyper);
 size_t riggs_cnode_backward_workspace_floats(int32_t N, int32_t M, int32_t K, int32_t hyper);
 int riggs_cnode_forward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t feat_stride, int32_t node_stride, int32_t flags,
                         const float* x, const float* feature, const float* motion_mask, const float* nodes,

@@ -1,6 +1,6 @@
 """Stage-1 control-node deformation with the reference's names (/root/reference/utils/time_utils.py:770-1236
 ``ControlNodeWarp``): K nearest control nodes per Gaussian in (xyz, hyper) space, Gaussian-kernel weights, blend of the nodes'
-translations / local-frame rotations / rotation and scale residuals — ONE HIP launch forward, two backward (csrc/cnode.hip)
+translations / local-frame rotations / rotation and scale residuals — ONE HIP launch forward, five backward (csrc/cnode.hip)
 instead of a KNN extension call, ~10 (N, K, ·) gathers, an einsum and autograd's replay of them.
 
 Covered: the configuration the trainer ships (KNN weights; ``local_frame``, ``d_rot_as_res``, ``with_node_weight``, ``hyper_dim``

@@ -18,11 +18,16 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// ---- library options -------------------------------------------------------------------
-static const char* kOptNames[OPT_COUNT] = {"fwd_wide_tiles", "fwd_wide_min", "bin_grouped", "cnode_bwd_atomics", "color_side_jobs", "preprocess_bwd_lean", "pose_mlp_layered", "fwd_hist_view_tol", "lbs_scalar"};
-static const int kOptDefaults[OPT_COUNT] = {256, 4096, -1, 0, 1, -1, 0, 20, 0};
-static int g_opt[OPT_COUNT] = {256, 4096, -1, 0, 1, -1, 0, 20, 0};
-int option(int id) { return g_opt[id]; }
+// ---- library options: one record per OptId, in the enum's order.  With `accepts`, a value outside [lo, hi] fails and names it;
+// without, a negative value becomes the default (1 where hi is 1: those store "non-zero") and any value is brought into [lo, hi].
+static constexpr struct OptDef { const char* name; int def, lo, hi; const char* accepts; } kOpts[] = {
+    {"fwd_wide_tiles", 256, 0, 65535}, {"fwd_wide_min", 4096, 256, INT32_MAX},
+    {"bin_grouped", -1, -1, 1, "-1 (by size), 0 or 1"}, {"color_side_jobs", 1, 0, 1},
+    {"preprocess_bwd_lean", -1, -1, 1, "-1 (with cfg.sparse_zero), 0 or 1"}, {"pose_mlp_layered", 0, 0, 1},
+    {"fwd_hist_view_tol", 20, 0, INT32_MAX}, {"lbs_scalar", 0, -1, 1, "-1 (never), 0 (by size) or 1 (always)"}};
+static_assert(sizeof(kOpts) / sizeof(kOpts[0]) == OPT_COUNT, "kOpts needs one record per OptId");
+static auto g_opt = [] { struct { int v[OPT_COUNT]; } o{}; for (int i = 0; i < OPT_COUNT; i++) o.v[i] = kOpts[i].def; return o; }();
+int option(int id) { return g_opt.v[id]; }
 
 // ---- event-based kernel timing -------------------------------------------------------
 static const char* kProfNames[PROF_COUNT] = {
@@ -155,27 +160,24 @@ int riggs_prof_read(int32_t id, float* total_ms, int32_t* launches) {
 const char* riggs_last_error(void) { return g_err; }
 
 static int opt_id(const char* name) {
-  for (int i = 0; i < OPT_COUNT; i++) if (name && !strcmp(name, kOptNames[i])) return i;
+  for (int i = 0; i < OPT_COUNT; i++) if (name && !strcmp(name, kOpts[i].name)) return i;
   return -1;
 }
 int riggs_set_option(const char* name, int32_t value) {
   const int id = opt_id(name);
   if (id < 0) { set_error("riggs_set_option: unknown option '%s'", name ? name : "(null)"); return 2; }
+  const OptDef& d = kOpts[id];
   int v = value;
-  if (id == OPT_FWD_WIDE_TILES) { if (v < 0) v = kOptDefaults[id]; if (v > 65535) v = 65535; }
-  if (id == OPT_FWD_WIDE_MIN) { if (v < 0) v = kOptDefaults[id]; if (v < 256) v = 256; }
-  if (id == OPT_FWD_HIST_VIEW_TOL) { if (v < 0) v = kOptDefaults[id]; }
-  if (id == OPT_BIN_GROUPED) { if (v < -1 || v > 1) { set_error("riggs_set_option: bin_grouped takes -1 (by size), 0 or 1"); return 2; } }
-  if (id == OPT_PREPROCESS_BWD_LEAN) { if (v < -1 || v > 1) { set_error("riggs_set_option: preprocess_bwd_lean takes -1 (with cfg.sparse_zero), 0 or 1"); return 2; } }
-  if (id == OPT_CNODE_BWD_ATOMICS || id == OPT_COLOR_SIDE_JOBS || id == OPT_POSE_MLP_LAYERED) v = v ? 1 : 0;
-  if (id == OPT_LBS_SCALAR) { if (v < -1 || v > 1) { set_error("riggs_set_option: lbs_scalar takes -1 (never), 0 (by size) or 1 (always)"); return 2; } }
-  g_opt[id] = v;
+  if (d.accepts && (v < d.lo || v > d.hi)) { set_error("riggs_set_option: %s takes %s", d.name, d.accepts); return 2; }
+  if (v < 0 && !d.accepts) v = d.hi == 1 ? 1 : d.def;
+  v = v < d.lo ? d.lo : (v > d.hi ? d.hi : v);
+  g_opt.v[id] = v;
   return 0;
 }
 int riggs_get_option(const char* name, int32_t* value) {
   const int id = opt_id(name);
   if (id < 0 || !value) { set_error("riggs_get_option: unknown option '%s'", name ? name : "(null)"); return 2; }
-  *value = g_opt[id];
+  *value = g_opt.v[id];
   return 0;
 }
 

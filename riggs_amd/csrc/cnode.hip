@@ -10,8 +10,7 @@
 // per-node inverse lists: a counting sort of the N K neighbour entries by node, a per-Gaussian pass that writes each entry's
 // 21 + hyper_dim contributions (translation, rotation, scale, dL/dR of the local frame, radius, node weight, hyper coordinates)
 // as a 128-byte row at the entry's sorted position, and one workgroup per node that sums its contiguous rows and applies the
-// node-level chain rules (quaternion -> matrix, exp, sigmoid).  The first backward (LDS float atomics + per-workgroup partial
-// tables) is kept behind riggs_set_option("cnode_bwd_atomics", 1): the LDS executes float atomics lane by lane.  Forward is issue-bound by the
+// node-level chain rules (quaternion -> matrix, exp, sigmoid): five launches, no float atomics.  Forward is issue-bound by the
 // scan (N M (3 + hyper) FMAs); the tables it reads are L2-resident.
 #include "common.h"
 
@@ -39,9 +38,7 @@ struct CNodeArgs {
   const float* g_xyz; const float* g_rot; const float* g_scale;  // upstream, each may be NULL
   float* g_feature;   // (N, feat_stride) or NULL
   float* g_mask;      // (N) or NULL
-  float* partial;     // (blocks, M, nacc)
-  int nacc;
-  // inverse-list backward
+  // the backward's inverse lists
   float4* rows;       // (N K, 8) float4: the 21 + hyper contributions of every neighbour entry, grouped by node
   int* sorted;        // (N K) position of every entry in the node-grouped order
   int* hist;          // (list blocks, M) entry counts -> exclusive offsets inside the node's segment
@@ -166,17 +163,11 @@ __global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
 #define CN_ACC_FIXED 21
 #define CN_BWD_THREADS 1024
 
-// LISTS = false: per-node gradients through LDS float atomics + one partial table per workgroup (the first version; the LDS
-// executes float atomics lane by lane).  LISTS = true: only the per-Gaussian outputs and four scalars per neighbour entry are
-// written; the per-node sums are made by cnode_node_reduce_kernel over inverse lists.
-template <int K, bool LISTS>
+// The per-Gaussian pass: a thread writes its Gaussian's outputs (g_feature, g_mask) and, for each of its K neighbour entries, the
+// entry's accumulator row at the entry's position in the node-grouped order (a.sorted); the per-node sums are made by
+// cnode_node_reduce_kernel over those rows.
+template <int K>
 __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArgs a) {
-  extern __shared__ float s_acc[];  // (M, nacc)
-  const int nacc = a.nacc;
-  if (!LISTS) {
-    for (int e = threadIdx.x; e < a.M * nacc; e += CN_BWD_THREADS) s_acc[e] = 0.f;
-    __syncthreads();
-  }
   const bool local = a.flags & CN_LOCAL_FRAME;
   const float bias = (a.flags & CN_ROT_AS_RES) ? 0.f : 1.f;
   for (int i = blockIdx.x * CN_BWD_THREADS + threadIdx.x; i < a.N; i += gridDim.x * CN_BWD_THREADS) {
@@ -217,14 +208,6 @@ __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArg
           y0 += R[0] * r0 + R[1] * r1 + R[2] * r2 + n0;
           y1 += R[3] * r0 + R[4] * r1 + R[5] * r2 + n1;
           y2 += R[6] * r0 + R[7] * r1 + R[8] * r2 + n2;
-          // dL/dR += w (g m) (x - n)^T
-          if (!LISTS) {
-          float* acc = s_acc + (size_t)n * nacc + 10;
-          const float wg0 = w[k] * g[0] * m, wg1 = w[k] * g[1] * m, wg2 = w[k] * g[2] * m;
-          atomicAdd(acc + 0, wg0 * r0); atomicAdd(acc + 1, wg0 * r1); atomicAdd(acc + 2, wg0 * r2);
-          atomicAdd(acc + 3, wg1 * r0); atomicAdd(acc + 4, wg1 * r1); atomicAdd(acc + 5, wg1 * r2);
-          atomicAdd(acc + 6, wg2 * r0); atomicAdd(acc + 7, wg2 * r1); atomicAdd(acc + 8, wg2 * r2);
-          }
         }
         const float ro0 = a.rot[4 * n] + bias, ro1 = a.rot[4 * n + 1], ro2 = a.rot[4 * n + 2], ro3 = a.rot[4 * n + 3];
         const float c0 = a.scale[3 * n], c1 = a.scale[3 * n + 1], c2 = a.scale[3 * n + 2];
@@ -233,13 +216,6 @@ __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArg
         ts[0] += w[k] * y0; ts[1] += w[k] * y1; ts[2] += w[k] * y2;
         rs[0] += w[k] * ro0; rs[1] += w[k] * ro1; rs[2] += w[k] * ro2; rs[3] += w[k] * ro3;
         ss[0] += w[k] * c0; ss[1] += w[k] * c1; ss[2] += w[k] * c2;
-        if (!LISTS) {
-        float* acc = s_acc + (size_t)n * nacc;
-        const float wm = w[k] * m;
-        atomicAdd(acc + 0, wm * g[0]); atomicAdd(acc + 1, wm * g[1]); atomicAdd(acc + 2, wm * g[2]);
-        atomicAdd(acc + 3, wm * h[0]); atomicAdd(acc + 4, wm * h[1]); atomicAdd(acc + 5, wm * h[2]); atomicAdd(acc + 6, wm * h[3]);
-        atomicAdd(acc + 7, wm * s[0]); atomicAdd(acc + 8, wm * s[1]); atomicAdd(acc + 9, wm * s[2]);
-        }
       }
     }
     if (a.g_mask) {
@@ -258,13 +234,10 @@ __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArg
         const int n = a.nn_idx[(size_t)i * K + k];
         const float dist = a.nn_dist[(size_t)i * K + k];
         const float dv = (dw[k] - wdw) / vsum;
-        float* acc = s_acc + (size_t)n * nacc;
         const float dd = dv * u[k] * (-1.0f / (2.0f * r2_[k]));
         float row[32];
 #pragma unroll
         for (int c = 0; c < 32; ++c) row[c] = 0.f;
-        if (!LISTS) atomicAdd(acc + 19, dv * u[k] * dist / r2_[k]);
-        if (!LISTS && a.weight_logit) atomicAdd(acc + 20, dv * e_[k]);
         if (a.hyper > 0) {
 #pragma unroll
           for (int d = 0; d < 13; ++d) {
@@ -272,28 +245,26 @@ __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArg
               const float diff = a.feature[(size_t)i * a.feat_stride + d] - a.nodes[(size_t)n * a.node_stride + 3 + d];
               const float v = dd * 2.0f * diff;
               gf[d] += v;
-              if (!LISTS) atomicAdd(acc + CN_ACC_FIXED + d, -v);
-              if (LISTS) row[CN_ACC_FIXED + d] = -v;
+              row[CN_ACC_FIXED + d] = -v;
             }
           }
         }
-        if (LISTS) {
-          const float c1 = w[k] * m;
-          row[0] = c1 * g[0]; row[1] = c1 * g[1]; row[2] = c1 * g[2];
-          row[3] = c1 * h[0]; row[4] = c1 * h[1]; row[5] = c1 * h[2]; row[6] = c1 * h[3];
-          row[7] = c1 * s[0]; row[8] = c1 * s[1]; row[9] = c1 * s[2];
-          if (local) {
+        const float c1 = w[k] * m;
+        row[0] = c1 * g[0]; row[1] = c1 * g[1]; row[2] = c1 * g[2];
+        row[3] = c1 * h[0]; row[4] = c1 * h[1]; row[5] = c1 * h[2]; row[6] = c1 * h[3];
+        row[7] = c1 * s[0]; row[8] = c1 * s[1]; row[9] = c1 * s[2];
+        if (local) {
+          // dL/dR = w (g m) (x - n)^T
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-              row[10 + 3 * r] = c1 * g[r] * rel[k][0]; row[11 + 3 * r] = c1 * g[r] * rel[k][1]; row[12 + 3 * r] = c1 * g[r] * rel[k][2];
-            }
+          for (int r = 0; r < 3; ++r) {
+            row[10 + 3 * r] = c1 * g[r] * rel[k][0]; row[11 + 3 * r] = c1 * g[r] * rel[k][1]; row[12 + 3 * r] = c1 * g[r] * rel[k][2];
           }
-          row[19] = dv * u[k] * dist / r2_[k];
-          row[20] = dv * e_[k];
-          float4* dst = a.rows + 8 * (size_t)a.sorted[(size_t)i * K + k];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) dst[q] = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
         }
+        row[19] = dv * u[k] * dist / r2_[k];
+        row[20] = dv * e_[k];
+        float4* dst = a.rows + 8 * (size_t)a.sorted[(size_t)i * K + k];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) dst[q] = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
       }
     }
     if (a.g_feature) {
@@ -302,14 +273,9 @@ __global__ void __launch_bounds__(CN_BWD_THREADS) cnode_backward_kernel(CNodeArg
       for (int d = 0; d < 13; ++d) if (d < a.hyper) a.g_feature[(size_t)i * a.feat_stride + d] = gf[d];
     }
   }
-  if (!LISTS) {
-    __syncthreads();
-    float* out = a.partial + (size_t)blockIdx.x * a.M * nacc;
-    for (int e = threadIdx.x; e < a.M * nacc; e += CN_BWD_THREADS) out[e] = s_acc[e];
-  }
 }
 
-// ---- inverse lists: a counting sort of the N K neighbour entries by node (M <= 2730 bins live in LDS) ---------------------
+// ---- inverse lists: a counting sort of the N K neighbour entries by node (M <= 4096 bins live in LDS) ---------------------
 #define CN_LIST_CHUNK 4096  // entries per workgroup of the histogram / scatter passes
 
 __global__ void __launch_bounds__(256) cnode_list_hist_kernel(CNodeArgs a) {
@@ -426,36 +392,6 @@ __global__ void __launch_bounds__(CN_NODE_THREADS) cnode_node_reduce_kernel(CNod
   if (threadIdx.x < 32) cn_node_chain(a, o, n, s_row, threadIdx.x);
 }
 
-// 8 nodes per workgroup, 32 lanes per node: lane c sums column c of the workgroups' partial tables in a fixed order, then the
-// node-level chain rules.
-__global__ void __launch_bounds__(256) cnode_finish_kernel(CNodeArgs a, CNodeGrads o, int blocks) {
-  __shared__ float s_v[8][32];
-  const int nl = threadIdx.x >> 5, c = threadIdx.x & 31;
-  const int n = blockIdx.x * 8 + nl;
-  float v = 0.f;
-  if (n < a.M && c < a.nacc) {
-    // four interleaved accumulators, eight loads in flight: a fixed order, but not one load latency per term
-    float v4[4] = {0.f, 0.f, 0.f, 0.f};
-    const float* src = a.partial + (size_t)n * a.nacc + c;
-    const size_t step = (size_t)a.M * a.nacc;
-    int b = 0;
-    for (; b + 8 <= blocks; b += 8) {
-      float t[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t[q] = src[(size_t)(b + q) * step];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v4[q & 3] += t[q];
-    }
-    for (; b < blocks; ++b) v4[b & 3] += src[(size_t)b * step];
-    v = (v4[0] + v4[1]) + (v4[2] + v4[3]);
-  }
-  s_v[nl][c] = v;
-  __syncthreads();
-  if (n >= a.M) return;
-  const float* S = s_v[nl];
-  cn_node_chain(a, o, n, S, c);
-}
-
 static int cn_check(int N, int M, int K, int hyper, int feat_stride, int node_stride, const void* feature) {
   RIGGS_REQUIRE(N >= 0 && M >= 1, "bad sizes");
   RIGGS_REQUIRE(K >= 1 && K <= CN_KMAX && K <= M, "K must be 1..8 and at most the number of nodes");
@@ -463,6 +399,19 @@ static int cn_check(int N, int M, int K, int hyper, int feat_stride, int node_st
   RIGGS_REQUIRE(node_stride >= 3 + hyper, "nodes need 3 + hyper_dim columns");
   RIGGS_REQUIRE(hyper == 0 || (feature && feat_stride >= hyper), "feature needs hyper_dim columns");
   return 0;
+}
+
+// what the forward and the backward both pass; everything else starts as NULL / 0
+static CNodeArgs cn_args(int N, int M, int K, int hyper, int feat_stride, int node_stride, int flags, const float* x,
+                         const float* feature, const float* motion_mask, const float* nodes, const float* node_radius_log,
+                         const float* node_weight_logit, const float* node_trans, const float* node_rot, const float* node_scale,
+                         const float* local_rot) {
+  CNodeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.N = N; a.M = M; a.K = K; a.hyper = hyper; a.feat_stride = feat_stride; a.node_stride = node_stride; a.flags = flags;
+  a.x = x; a.feature = feature; a.mask = motion_mask; a.nodes = nodes; a.radius_log = node_radius_log;
+  a.weight_logit = node_weight_logit; a.trans = node_trans; a.rot = node_rot; a.scale = node_scale; a.local_rot = local_rot;
+  return a;
 }
 
 template <int K>
@@ -483,25 +432,15 @@ using namespace riggs;
 
 extern "C" {
 
-// workgroups of the persistent backward grid: one per CU, two where two gradient tables fit a CU's LDS
-int riggs_cnode_backward_blocks(int32_t N, int32_t M, int32_t hyper) {
-  const int want = (N + CN_BWD_THREADS - 1) / CN_BWD_THREADS;
-  const int cap = (size_t)M * (CN_ACC_FIXED + hyper) * sizeof(float) <= 78 * 1024 ? 512 : 256;
-  return want < 1 ? 1 : (want > cap ? cap : want);
-}
-
 static int cn_list_blocks(int N, int K) {
   const long long total = (long long)N * K;
   const int b = (int)((total + CN_LIST_CHUNK - 1) / CN_LIST_CHUNK);
   return b < 1 ? 1 : b;
 }
 
-static bool cn_use_lists() { return option(OPT_CNODE_BWD_ATOMICS) == 0; }
-
+// rows (32 floats per entry) | sorted (N K) | hist (list blocks, M) | node_off (M + 1) | 8 spare; `hyper` does not enter
 size_t riggs_cnode_backward_workspace_floats(int32_t N, int32_t M, int32_t K, int32_t hyper) {
-  const size_t atomics = (size_t)riggs_cnode_backward_blocks(N, M, hyper) * M * (CN_ACC_FIXED + hyper);
-  const size_t lists = 33 * (size_t)N * K + (size_t)cn_list_blocks(N, K) * M + (size_t)M + 1 + 8;
-  return atomics > lists ? atomics : lists;
+  return 33 * (size_t)N * K + (size_t)cn_list_blocks(N, K) * M + (size_t)M + 1 + 8;
 }
 
 int riggs_cnode_forward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t feat_stride, int32_t node_stride, int32_t flags,
@@ -516,11 +455,8 @@ int riggs_cnode_forward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t 
                 nn_weight && nn_dist, "NULL buffer");
   const int dp4 = (3 + hyper + 3) / 4;
   RIGGS_REQUIRE((size_t)M * dp4 * 16 <= 128 * 1024, "control nodes do not fit the 128 KB LDS table");
-  CNodeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.N = N; a.M = M; a.K = K; a.hyper = hyper; a.feat_stride = feat_stride; a.node_stride = node_stride; a.flags = flags;
-  a.x = x; a.feature = feature; a.mask = motion_mask; a.nodes = nodes; a.radius_log = node_radius_log;
-  a.weight_logit = node_weight_logit; a.trans = node_trans; a.rot = node_rot; a.scale = node_scale; a.local_rot = local_rot;
+  CNodeArgs a = cn_args(N, M, K, hyper, feat_stride, node_stride, flags, x, feature, motion_mask, nodes, node_radius_log,
+                        node_weight_logit, node_trans, node_rot, node_scale, local_rot);
   a.d_xyz = d_xyz; a.d_rot = d_rot; a.d_scale = d_scale; a.nn_idx = nn_idx; a.nn_weight = nn_weight; a.nn_dist = nn_dist;
   hipStream_t s = (hipStream_t)stream;
   static unsigned long long attr_set = 0ull;
@@ -556,60 +492,32 @@ int riggs_cnode_backward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t
                 g_node_trans && g_node_rot && g_node_scale && g_node_radius_log && workspace, "NULL buffer");
   RIGGS_REQUIRE(!(flags & CN_LOCAL_FRAME) || local_rot, "local_frame needs local_rotation");
   RIGGS_REQUIRE(hyper == 0 || g_nodes_hyper, "NULL buffer");
-  CNodeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.N = N; a.M = M; a.K = K; a.hyper = hyper; a.feat_stride = feat_stride; a.node_stride = node_stride; a.flags = flags;
-  a.x = x; a.feature = feature; a.mask = motion_mask; a.nodes = nodes; a.radius_log = node_radius_log;
-  a.weight_logit = node_weight_logit; a.trans = node_trans; a.rot = node_rot; a.scale = node_scale; a.local_rot = local_rot;
+  RIGGS_REQUIRE(CN_ACC_FIXED + hyper <= 32, "accumulator row too wide");
+  RIGGS_REQUIRE(M <= 4096, "more than 4096 control nodes");
+  RIGGS_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  CNodeArgs a = cn_args(N, M, K, hyper, feat_stride, node_stride, flags, x, feature, motion_mask, nodes, node_radius_log,
+                        node_weight_logit, node_trans, node_rot, node_scale, local_rot);
   a.nn_idx = const_cast<int32_t*>(nn_idx); a.nn_dist = const_cast<float*>(nn_dist);
   a.g_xyz = g_xyz; a.g_rot = g_rot; a.g_scale = g_scale; a.g_feature = g_feature; a.g_mask = g_motion_mask;
-  a.partial = workspace; a.nacc = CN_ACC_FIXED + hyper;
-  RIGGS_REQUIRE(a.nacc <= 32, "accumulator row too wide");
   hipStream_t s = (hipStream_t)stream;
   CNodeGrads o = {g_node_trans, g_node_rot, g_node_scale, g_local_rot, g_node_radius_log,
                   node_weight_logit ? g_node_weight_logit : nullptr, g_nodes_hyper};
-#define CN_BLAUNCH(LISTS, grid, block, lds)                                                                          \
-  switch (K) {                                                                                                       \
-    case 1: hipLaunchKernelGGL((cnode_backward_kernel<1, LISTS>), grid, block, lds, s, a); break;                     \
-    case 2: hipLaunchKernelGGL((cnode_backward_kernel<2, LISTS>), grid, block, lds, s, a); break;                     \
-    case 3: hipLaunchKernelGGL((cnode_backward_kernel<3, LISTS>), grid, block, lds, s, a); break;                     \
-    case 4: hipLaunchKernelGGL((cnode_backward_kernel<4, LISTS>), grid, block, lds, s, a); break;                     \
-    case 5: hipLaunchKernelGGL((cnode_backward_kernel<5, LISTS>), grid, block, lds, s, a); break;                     \
-    case 6: hipLaunchKernelGGL((cnode_backward_kernel<6, LISTS>), grid, block, lds, s, a); break;                     \
-    case 7: hipLaunchKernelGGL((cnode_backward_kernel<7, LISTS>), grid, block, lds, s, a); break;                     \
-    default: hipLaunchKernelGGL((cnode_backward_kernel<8, LISTS>), grid, block, lds, s, a); break;                    \
-  }
-  if (cn_use_lists()) {
-    // (i) counting sort of the N K neighbour entries by node -> every entry's position; (ii) per-Gaussian pass: outputs of the
-    // Gaussians + each entry's 21 + hyper contributions as a 128-byte row at its position; (iii) one workgroup per node sums its
-    // (contiguous) rows
-    RIGGS_REQUIRE(M <= 4096, "more than 4096 control nodes");
-    RIGGS_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
-    a.list_blocks = cn_list_blocks(N, K);
-    a.rows = (float4*)workspace;
-    a.sorted = (int*)(workspace + 32 * (size_t)N * K);
-    a.hist = a.sorted + (size_t)N * K;
-    a.node_off = a.hist + (size_t)a.list_blocks * M;
-    hipLaunchKernelGGL(cnode_list_hist_kernel, dim3(a.list_blocks), dim3(256), (size_t)M * sizeof(int), s, a);
-    hipLaunchKernelGGL(cnode_list_scan_kernel, dim3(1), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(cnode_list_scatter_kernel, dim3(a.list_blocks), dim3(256), (size_t)M * sizeof(int), s, a);
-    const int gb = (N + CN_BWD_THREADS - 1) / CN_BWD_THREADS;
-    const dim3 grid(gb < 1 ? 1 : gb), block(CN_BWD_THREADS);
-    CN_BLAUNCH(true, grid, block, 0)
-    hipLaunchKernelGGL(cnode_node_reduce_kernel, dim3(M), dim3(CN_NODE_THREADS), 0, s, a, o);
-  } else {
-    const size_t lds = (size_t)M * a.nacc * sizeof(float);
-    RIGGS_REQUIRE(lds <= 160 * 1024 - 1024, "per-node gradient table does not fit LDS (M (21 + hyper_dim) floats <= 159 KB)");
-    static unsigned long long attr_set = 0ull;
-    if (once_per_device(attr_set)) {
-#define CN_BATTR(KK) RIGGS_HIP_CHECK(hipFuncSetAttribute((const void*)cnode_backward_kernel<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      CN_BATTR(1) CN_BATTR(2) CN_BATTR(3) CN_BATTR(4) CN_BATTR(5) CN_BATTR(6) CN_BATTR(7) CN_BATTR(8)
-    }
-    const int blocks = riggs_cnode_backward_blocks(N, M, hyper);
-    const dim3 grid(blocks), block(CN_BWD_THREADS);
-    CN_BLAUNCH(false, grid, block, lds)
-    hipLaunchKernelGGL(cnode_finish_kernel, dim3((M + 7) / 8), dim3(256), 0, s, a, o, blocks);
-  }
+  // (i) counting sort of the N K neighbour entries by node -> every entry's position; (ii) per-Gaussian pass: outputs of the
+  // Gaussians + each entry's 21 + hyper contributions as a 128-byte row at its position; (iii) one workgroup per node sums its
+  // (contiguous) rows
+  a.list_blocks = cn_list_blocks(N, K);
+  a.rows = (float4*)workspace;
+  a.sorted = (int*)(workspace + 32 * (size_t)N * K);
+  a.hist = a.sorted + (size_t)N * K;
+  a.node_off = a.hist + (size_t)a.list_blocks * M;
+  hipLaunchKernelGGL(cnode_list_hist_kernel, dim3(a.list_blocks), dim3(256), (size_t)M * sizeof(int), s, a);
+  hipLaunchKernelGGL(cnode_list_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(cnode_list_scatter_kernel, dim3(a.list_blocks), dim3(256), (size_t)M * sizeof(int), s, a);
+  const int gb = (N + CN_BWD_THREADS - 1) / CN_BWD_THREADS;
+  const dim3 grid(gb < 1 ? 1 : gb), block(CN_BWD_THREADS);
+#define CN_BLAUNCH(KK) case KK: hipLaunchKernelGGL(cnode_backward_kernel<KK>, grid, block, 0, s, a); break;
+  switch (K) { CN_BLAUNCH(1) CN_BLAUNCH(2) CN_BLAUNCH(3) CN_BLAUNCH(4) CN_BLAUNCH(5) CN_BLAUNCH(6) CN_BLAUNCH(7) CN_BLAUNCH(8) }
+  hipLaunchKernelGGL(cnode_node_reduce_kernel, dim3(M), dim3(CN_NODE_THREADS), 0, s, a, o);
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
 }

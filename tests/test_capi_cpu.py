@@ -155,6 +155,30 @@ def test_untyped_out_pointers_still_take_byref_and_arrays():
         _lib.set_option("fwd_wide_min", before)
     assert _lib.get_option("fwd_wide_min") == before
     assert L.riggs_get_option(b"no_such_option", C.byref(v)) != 0
+    # how each option takes a value: (set, stored) pairs; the last pair puts the default back
+    takes = {"fwd_wide_tiles": ((70000, 65535), (0, 0), (-1, 256)), "fwd_wide_min": ((100, 256), (0, 256), (-7, 4096)),
+             "fwd_hist_view_tol": ((0, 0), (10 ** 6, 10 ** 6), (-1, 20)), "color_side_jobs": ((0, 0), (5, 1), (-5, 1)),
+             "pose_mlp_layered": ((5, 1), (-5, 1), (0, 0)), "bin_grouped": ((1, 1), (0, 0), (-1, -1)),
+             "preprocess_bwd_lean": ((1, 1), (0, 0), (-1, -1)), "lbs_scalar": ((1, 1), (-1, -1), (0, 0))}
+    try:
+        for name, pairs in takes.items():
+            default = _lib.get_option(name)
+            assert default == pairs[-1][1], name
+            for given, stored in pairs:
+                assert L.riggs_set_option(name.encode(), given) == 0 and _lib.get_option(name) == stored, (name, given)
+        # the three with a closed set of values refuse anything else with rc 2, say which values they take, and keep what they had
+        for name, accepts in (("bin_grouped", b"bin_grouped takes -1 (by size), 0 or 1"),
+                              ("preprocess_bwd_lean", b"preprocess_bwd_lean takes -1 (with cfg.sparse_zero), 0 or 1"),
+                              ("lbs_scalar", b"lbs_scalar takes -1 (never), 0 (by size) or 1 (always)")):
+            for bad in (-2, 2):
+                assert L.riggs_set_option(name.encode(), bad) == 2 and accepts in L.riggs_last_error(), (name, bad)
+            assert _lib.get_option(name) == takes[name][-1][1]
+        assert L.riggs_set_option(b"no_such_option", 1) == 2 and b"unknown option 'no_such_option'" in L.riggs_last_error()
+    finally:
+        for name, pairs in takes.items():
+            _lib.set_option(name, pairs[-1][0])
+    # the option that selected the control-node backward's first design left with that design: an unknown name now
+    assert L.riggs_set_option(b"cnode_bwd_atomics", 1) != 0 and L.riggs_get_option(b"cnode_bwd_atomics", C.byref(v)) != 0
 
 
 def test_library_and_header_versions_agree(monkeypatch):
@@ -249,7 +273,7 @@ def test_argument_validation_of_the_next_row_entries_needs_no_gpu():
     assert L.riggs_cnode_forward(10, 32, 3, 0, 0, 3, 1, *([N] * 17)) != 0            # local_frame without local_rotation
     assert b"local_rotation" in L.riggs_last_error()
     assert L.riggs_cnode_backward_workspace_floats(1000, 64, 3, 8) >= 33 * 3000
-    assert 1 <= L.riggs_cnode_backward_blocks(10, 64, 8) <= L.riggs_cnode_backward_blocks(10 ** 6, 64, 8) <= 512
+    assert L.riggs_cnode_backward_workspace_floats(10, 64, 3, 8) == 1127  # 33 N K + one list block's M + M + 1 + 8
     # skeleton projection loss: one joint, empty sample / pixel sets, too many samples per bone
     for (j, s, m) in ((1, 4, 4), (5, 0, 4), (5, 4, 0), (5, 4096, 4)):
         rc = L.riggs_skeleton_projection_forward(j, s, m, N, N, N, N, 1.0, 1.0, 0.0, 0.0, N, N, N, N, N, N)

@@ -211,22 +211,6 @@ def test_stage1_iteration_through_the_rasterizer_matches_torch_blend():
         assert g.abs().max().item() > 0 and err <= 2e-3 * g.abs().max().item(), (k, err, g.abs().max().item())
 
 
-def test_atomics_backward_variant_passes_the_same_goldens():
-    """riggs_set_option("cnode_bwd_atomics", 1) selects the first backward (LDS float atomics + partial tables): the golden
-    and oracle cases once more with it (workspaces are sized per call, after the option is set)."""
-    from riggs_amd import _lib as L
-    assert L.get_option("cnode_bwd_atomics") == 0
-    L.set_option("cnode_bwd_atomics", 1)
-    try:
-        for name in NAMES:
-            test_module_matches_reference_golden(name)
-        test_against_oracle(20_000, 512, 3, 8, True, True, True, True)
-        test_against_oracle(3_001, 40, 8, 0, True, False, False, True)
-        test_against_oracle(1, 64, 3, 11, True, True, False, True)
-    finally:
-        L.set_option("cnode_bwd_atomics", 0)
-
-
 def test_pred_opacity_and_color_match_reference_golden():
     """KNN weights (HIP kernel) + the opacity / colour blends of time_utils.py:1214-1225, whose gradients reach the node radii,
     node weights, hyper coordinates and the Gaussians' feature through the weights themselves."""
