@@ -696,6 +696,8 @@ int riggs_node_projection_backward(int32_t J, int32_t M, const float* d_nodes, c
  * beyond `hyper` zero), motion_mask, the node attributes, _node_radius, _node_weight and the nodes' hyper coordinates
  * (M, hyper); xyz of Gaussians and nodes are detached in the reference (:944, :947-949, :1152).  workspace:
  * riggs_cnode_backward_workspace_floats = 33 N K + max(1, ceil(N K / 4096)) M + M + 1 + 8 floats, 16-byte aligned; M <= 4096.
+ * N = 0: every per-Gaussian pointer may be NULL (an empty tensor has no storage); the forward returns, the backward writes
+ * zero node gradients.
  * ===================================================================== */
 size_t riggs_cnode_backward_workspace_floats(int32_t N, int32_t M, int32_t K, int32_t hyper);
 int riggs_cnode_forward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t feat_stride, int32_t node_stride, int32_t flags,

@@ -53,7 +53,8 @@ def quat_to_mat_vjp(q, G):
     return dq
 
 
-def cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim):
+def cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim, nn_idx=None):
+    """``nn_idx`` (N, K): use these neighbour lists (a kernel's own) instead of the K smallest distances."""
     x = np.asarray(x, np.float64)
     nodes = np.asarray(nodes, np.float64)
     if hyper_dim > 0 and feature is not None and np.size(feature):
@@ -62,7 +63,7 @@ def cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hype
     else:
         xa, na = x, nodes[:, :3]
     d = ((xa[:, None, :] - na[None, :, :]) ** 2).sum(-1)
-    idx = np.argsort(d, axis=1, kind="stable")[:, :K]
+    idx = np.argsort(d, axis=1, kind="stable")[:, :K] if nn_idx is None else np.asarray(nn_idx, np.int64).reshape(x.shape[0], K)
     dist = np.take_along_axis(d, idx, 1)
     r = np.exp(np.asarray(node_radius_log, np.float64))[idx]
     u = np.exp(-dist / (2 * r * r))
@@ -72,11 +73,12 @@ def cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hype
     return v / v.sum(-1, keepdims=True), dist, idx
 
 
-def forward(x, feature, mask, nodes, node_radius_log, node_weight_logit, attrs, K, hyper_dim, local_frame, d_rot_as_res):
+def forward(x, feature, mask, nodes, node_radius_log, node_weight_logit, attrs, K, hyper_dim, local_frame, d_rot_as_res,
+            nn_idx=None):
     x = np.asarray(x, np.float64)
     nodes = np.asarray(nodes, np.float64)
     m = np.asarray(mask, np.float64).reshape(-1, 1)
-    w, dist, idx = cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim)
+    w, dist, idx = cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim, nn_idx)
     tr, rot, sc = (np.asarray(attrs[k], np.float64) for k in ("d_xyz", "d_rotation", "d_scaling"))
     if local_frame:
         R = quat_to_mat(np.asarray(attrs["local_rotation"], np.float64) + E)
@@ -94,13 +96,14 @@ def forward(x, feature, mask, nodes, node_radius_log, node_weight_logit, attrs, 
             "nn_weight": w, "nn_dist": dist, "nn_idx": idx}
 
 
-def backward(x, feature, mask, nodes, node_radius_log, node_weight_logit, attrs, K, hyper_dim, local_frame, d_rot_as_res, gout):
+def backward(x, feature, mask, nodes, node_radius_log, node_weight_logit, attrs, K, hyper_dim, local_frame, d_rot_as_res, gout,
+             nn_idx=None):
     """gout: dict of upstream gradients for d_xyz, d_rotation, d_scaling, d_nodes -> dict of gradients."""
     x = np.asarray(x, np.float64)
     nodes = np.asarray(nodes, np.float64)
     M = nodes.shape[0]
     m = np.asarray(mask, np.float64).reshape(-1, 1)
-    w, dist, idx = cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim)
+    w, dist, idx = cal_nn_weight(x, feature, nodes, node_radius_log, node_weight_logit, K, hyper_dim, nn_idx)
     tr, rot, sc = (np.asarray(attrs[k], np.float64) for k in ("d_xyz", "d_rotation", "d_scaling"))
     lq = np.asarray(attrs["local_rotation"], np.float64) + E
     g, h, s_ = (np.asarray(gout[k], np.float64) for k in ("d_xyz", "d_rotation", "d_scaling"))

@@ -397,7 +397,7 @@ static int cn_check(int N, int M, int K, int hyper, int feat_stride, int node_st
   RIGGS_REQUIRE(K >= 1 && K <= CN_KMAX && K <= M, "K must be 1..8 and at most the number of nodes");
   RIGGS_REQUIRE(hyper >= 0 && hyper <= 11, "hyper_dim must be 0..11");
   RIGGS_REQUIRE(node_stride >= 3 + hyper, "nodes need 3 + hyper_dim columns");
-  RIGGS_REQUIRE(hyper == 0 || (feature && feat_stride >= hyper), "feature needs hyper_dim columns");
+  RIGGS_REQUIRE(hyper == 0 || ((feature || N == 0) && feat_stride >= hyper), "feature needs hyper_dim columns");
   return 0;
 }
 
@@ -488,7 +488,9 @@ int riggs_cnode_backward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t
                          float* g_local_rot, float* g_node_radius_log, float* g_node_weight_logit, float* g_nodes_hyper,
                          float* workspace, riggs_stream stream) {
   if (int rc = cn_check(N, M, K, hyper, feat_stride, node_stride, feature)) return rc;
-  RIGGS_REQUIRE(x && nodes && node_radius_log && node_trans && node_rot && node_scale && (N == 0 || (nn_idx && nn_dist)) &&
+  // (the per-Gaussian buffers of an empty selection may be NULL: an empty tensor has no storage; the launches do nothing for N = 0
+  // but write the zero node gradients)
+  RIGGS_REQUIRE(nodes && node_radius_log && node_trans && node_rot && node_scale && (N == 0 || (x && nn_idx && nn_dist)) &&
                 g_node_trans && g_node_rot && g_node_scale && g_node_radius_log && workspace, "NULL buffer");
   RIGGS_REQUIRE(!(flags & CN_LOCAL_FRAME) || local_rot, "local_frame needs local_rotation");
   RIGGS_REQUIRE(hyper == 0 || g_nodes_hyper, "NULL buffer");

@@ -177,3 +177,27 @@ def check_full_size_properties(act, cam):
     inv = radii == 0
     assert float(g1[0][inv].abs().max() if inv.any() else 0.0) == 0.0
     return R, int((radii > 0).sum())
+
+
+# ---- buffers of the C-ABI tests: outputs in front of a sentinel tail, per-row inputs in front of a NaN tail
+SENT = 1234.5678
+TAIL = 67
+
+
+def out_buf(shape, dtype=torch.float32, fill=SENT):
+    """A view of `shape` at the front of a buffer with TAIL extra rows of sentinel."""
+    rows = shape[0] if shape else 1
+    buf = torch.full((rows + TAIL,) + tuple(shape[1:]), fill, dtype=dtype, device="cuda")
+    return buf[:rows].view(shape) if shape else buf[:1], buf
+
+
+def tail_intact(buf, rows, fill=SENT):
+    t = buf[rows:]
+    return bool((t == fill).all())
+
+
+def in_buf(t):
+    """A device copy of the per-row input `t` followed by TAIL rows of NaN."""
+    buf = torch.full((t.shape[0] + TAIL,) + tuple(t.shape[1:]), float("nan"), dtype=torch.float32, device="cuda")
+    buf[:t.shape[0]] = t.cuda()
+    return buf[:t.shape[0]], buf
