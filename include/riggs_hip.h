@@ -1227,6 +1227,37 @@ int32_t riggs_node_semantic_tile(int32_t F);
 int riggs_node_semantic_labels(int32_t F, int32_t M, const float* d_nodes, const void* cameras /* device: F records */,
                                float* labels, int32_t* median, riggs_stream stream);
 
+/* =====================================================================
+ * Inverse kinematics on the rig's chain (csrc/ik.hip; riggs_amd/pose_edit.py: solve_ik): turn the joints so that up to
+ * RIGGS_IK_MAX_HANDLES handle joints reach their targets.  Damped least squares (Wampler 1986) with the clamped target step of
+ * Buss & Kim (2005), restated from the published method (the reference's editor turns one joint at a time and has no IK);
+ * tests/ik_ref.py is the NumPy restatement.  Added symbols: RIGGS_ABI_VERSION is unchanged.
+ *
+ * B problems on one skeleton: joints (J,3), parents (J) as riggs_fk_forward takes them (parents[i] < i; a value outside [0, i)
+ * is clamped into it), 1 <= J <= 256, 1 <= E <= RIGGS_IK_MAX_HANDLES.  Per problem b: local_rot_in (B,J,4) un-normalised wxyz,
+ * global_trans_in (B,3), handles (B,E) joint indices, targets (B,E,3), weights (B,E) or NULL (all 1): a weight <= 0 (or NaN)
+ * switches its handle off, and so does a handle index outside [0, J), whose residual is NaN.  locked (J) bytes or NULL: a joint
+ * with a non-zero byte keeps its quaternion, bit for bit, as does every joint on no live handle's path root .. handle.
+ * `iterations` >= 0 steps of: forward kinematics; per live handle d = target - posed, shortened to max_step, r = sqrt(w) d; the
+ * Jacobian blocks -sqrt(w) [posed_handle - pivot_a]x of the unlocked joints a on the handle's path (pivot_a: the posed parent,
+ * the root's own position), with solve_translation a further block sqrt(w) I; (J J^T + damping^2 I) y = r by Cholesky;
+ * omega_a = J_a^T y turned into the parent's frame, theta = |.|, and q_a <- (cos theta/2, sin(theta/2) axis) (x) q_a where
+ * theta > 0; global_trans += sum sqrt(w) y with solve_translation.  Then one more forward kinematics:
+ * local_rot_out (B,J,4), global_trans_out (B,3), d_nodes (B,J,3) the posed joints, residual (B,E) = |target - posed handle|.
+ * The outputs may alias the inputs of the same shape.
+ * damping > 0 and max_step >= 0 are host values; bit 0 (bit 1) of `relative` multiplies damping (max_step) by the device float
+ * *extent (read by the kernel: nothing is read back), which is only needed then.
+ * One workgroup per problem, all iterations in ONE launch on `stream` (J <= 64: one wave; else 256 threads); no float atomics:
+ * the same inputs give the same bits, and a problem's result does not depend on the rest of the batch.  Does not allocate, read
+ * back or synchronise: legal inside a stream capture.
+ * ===================================================================== */
+#define RIGGS_IK_MAX_HANDLES 8
+int riggs_ik_solve(int32_t B, int32_t J, int32_t E, const float* joints, const int32_t* parents, const float* local_rot_in,
+                   const float* global_trans_in, const int32_t* handles, const float* targets, const float* weights,
+                   const uint8_t* locked, int32_t iterations, float damping, float max_step, const float* extent, int32_t relative,
+                   int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
+                   riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

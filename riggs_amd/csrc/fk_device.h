@@ -398,4 +398,58 @@ __device__ __forceinline__ void fk_block_backward(int J, const FkIn& in, const F
   fk_dq_from_dT(on, in, dT, dq);
 }
 
+// ---- the level sweep alone, for a caller that changes the rotations and runs the chain again (ik.hip: once per iteration).
+// `f` (and `sh`) come from an earlier fk_wave_forward / fk_block_forward over the same parents, whose topology — levels,
+// children, the deepest level — is kept; the local transforms are renewed from in.q and the sweep G_i = G_parent(i) T_i is the
+// forward's, operation for operation.  Call with all lanes (threads) of the wave (workgroup).
+__device__ __forceinline__ void fk_wave_sweep(int J, const FkIn& in, FkLane& f) {
+  const int j = threadIdx.x & 63;
+  if (j < J) fk_local_T(in, f.T);
+#pragma unroll
+  for (int e = 0; e < 12; e++) f.G[e] = f.T[e];
+  for (int l = 1; l <= f.maxlev; l++) {
+    float Gp[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) Gp[e] = fk_lane_get(f.G[e], f.par);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        float v = Gp[4 * r] * f.T[c] + Gp[4 * r + 1] * f.T[4 + c] + Gp[4 * r + 2] * f.T[8 + c];
+        if (c == 3) v += Gp[4 * r + 3];
+        if (j >= 1) f.G[4 * r + c] = v;
+      }
+  }
+}
+
+// ... over the block: sh.G is rewritten (behind a barrier: the previous sweep's readers are done) and final behind the last one.
+__device__ __forceinline__ void fk_block_sweep(int J, const FkIn& in, FkWide& f, FkWideShared& sh) {
+  const int j = threadIdx.x;
+  const bool on = j < J;
+  if (on) fk_local_T(in, f.T);
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 12; e++) sh.G[j][e] = f.T[e];
+  __syncthreads();
+  for (int l = 1; l <= f.maxlev; l++) {
+    if (on && f.lev == l) {
+      float Gp[12];
+#pragma unroll
+      for (int e = 0; e < 12; e++) Gp[e] = sh.G[f.par][e];
+      float G[12];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          float v = Gp[4 * r] * f.T[c] + Gp[4 * r + 1] * f.T[4 + c] + Gp[4 * r + 2] * f.T[8 + c];
+          if (c == 3) v += Gp[4 * r + 3];
+          G[4 * r + c] = v;
+        }
+#pragma unroll
+      for (int e = 0; e < 12; e++) sh.G[j][e] = G[e];
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace riggs

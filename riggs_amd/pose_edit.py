@@ -1,0 +1,243 @@
+"""Editing the pose of a trained rig by hand: the editor's joint drag, and inverse kinematics on the device.
+
+The first four functions mirror the reference editor's edit step (``interactive_GUI.py``): ``callback_keypoint_drag`` :1268-1329
+turns ONE picked joint about the view axis (``update_edited_skeleton_pose`` :324-344, ``update_skeleton_pose_by_rotation``
+:296-321) and the edit is composed onto the pose of the frame (:397-399, :440-442).  The reference does this on the host, with
+NumPy, scipy and two read-backs per mouse event; here it is torch ops that never read back (CPU tensors work as well), so
+``viewer.pick_joint``'s device scalar can be handed on as it is.
+
+``solve_ik`` is what the reference lacks: drag up to 8 end effectors and let the chain follow — damped least squares (Wampler
+1986) with Buss & Kim's clamped target step on the rig's own kinematics, every iteration inside ONE launch of csrc/ik.hip
+(include/riggs_hip.h: riggs_ik_solve; tests/ik_ref.py is the NumPy restatement).  Inference only."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .dual_quaternion import quaternion_multiply
+
+MAX_HANDLES, MAX_JOINTS = L.CONSTANTS["RIGGS_IK_MAX_HANDLES"], 256
+
+
+# --------------------------------------------------------------------------- the reference's edit step
+def _matrix(camera, name, like=None):
+    m = getattr(camera, name)
+    return m if like is None else m.to(like.device)
+
+
+def view_axis(camera):
+    """:337-339 — ``([0, 0, 1, 1] @ inverse(full_proj_transform))[:3]``, normalised: the axis the editor turns a joint about."""
+    m = _matrix(camera, "full_proj_transform").float()
+    d = (torch.tensor([[0.0, 0.0, 1.0, 1.0]], dtype=m.dtype, device=m.device) @ torch.inverse(m))[0, :3]
+    return d / d.norm()
+
+
+def _project_editor(camera, points):
+    """The editor's projection (:1314-1316; x is scaled by ``image_height`` and y by ``image_width``, as the reference writes it):
+    ``viewer._project(want_uv=True)`` on the device, the same rule in torch ops for CPU tensors."""
+    if points.is_cuda:
+        from . import viewer
+        return viewer._project(camera, points, viewer.LAYOUT_SQUARES, want_table=False, want_uv=True)[1]
+    m = _matrix(camera, "full_proj_transform", points).float()
+    hom = torch.cat([points, torch.ones_like(points[:, :1])], dim=1) @ m
+    return (hom[:, :2] / hom[:, 3:] + 1) / 2 * torch.tensor([float(camera.image_height), float(camera.image_width)], device=points.device)
+
+
+@torch.no_grad()
+def joint_drag(camera, d_nodes, parents, joint, mouse_xy, mouse_delta=None, cam_rot=None):
+    """:1296-1325 — what a drag of the picked ``joint`` to the mouse position means: ``(angle, translation)``, a 0-d and a (3,)
+    tensor on ``d_nodes``'s device.
+
+    The root joint (index 0; ``parents[0] < 0`` in the reference): angle 0 and ``0.001 * cam_rot @ [dx, -dy, 0]`` with
+    ``mouse_delta = (dx, dy)`` and ``cam_rot`` the (3, 3) camera rotation (:1302-1305).  Any other joint: translation 0 and the
+    signed angle in the image between (parent -> joint) and (parent -> mouse), its sign that of the 2-D cross product
+    (:1307-1325); ``mouse_xy`` is truncated to integers as the reference does (:1300).  ``joint`` may be a Python integer or a
+    0-d integer tensor (``viewer.pick_joint``'s); both cases are evaluated and selected on the device, nothing is read back.
+    One deviation: the cosine is clamped to [-1, 1] before ``acos`` — rounding can take the reference's just past 1, which gives NaN."""
+    d_nodes = d_nodes.detach().float()
+    dev = d_nodes.device
+    joint = torch.as_tensor(joint, device=dev).long().reshape(())
+    parents = torch.as_tensor(parents, device=dev).long()
+    parent = parents[joint].clamp(min=0)
+    uv = _project_editor(camera, d_nodes.contiguous())
+    mouse = torch.tensor([float(int(mouse_xy[0])), float(int(mouse_xy[1]))], device=dev)
+    vec_a = uv[joint] - uv[parent]
+    vec_b = mouse - uv[parent]
+    cos = (vec_a * vec_b).sum() / (vec_a.norm() * vec_b.norm() + 1e-16)
+    angle = torch.acos(cos.clamp(-1.0, 1.0))
+    cross = vec_a[0] * vec_b[1] - vec_a[1] * vec_b[0]
+    angle = torch.where(cross < 0, -angle, angle)
+    is_root = joint == 0
+    trans = torch.zeros(3, device=dev)
+    if mouse_delta is not None:
+        rot = torch.eye(3, device=dev) if cam_rot is None else torch.as_tensor(cam_rot, dtype=torch.float32, device=dev)[:3, :3]
+        trans = 0.001 * rot @ torch.tensor([float(mouse_delta[0]), -float(mouse_delta[1]), 0.0], device=dev)
+    zero = torch.zeros((), device=dev)
+    return torch.where(is_root, zero, angle), torch.where(is_root, trans, torch.zeros_like(trans))
+
+
+def rotvec_to_quaternion(rotvec):
+    """``scipy.spatial.transform.Rotation.from_rotvec(v).as_quat()`` reordered to wxyz (:298-300, :320), in torch ops: the unit
+    quaternion (cos(t/2), sin(t/2) v / t), t = |v|, with scipy's series sin(t/2)/t = 1/2 - t^2/48 + t^4/3840 below t = 1e-3."""
+    t = rotvec.norm(dim=-1, keepdim=True)
+    t2 = t * t
+    small = t <= 1e-3
+    k = torch.where(small, 0.5 - t2 / 48 + t2 * t2 / 3840, torch.sin(t / 2) / torch.where(small, torch.ones_like(t), t))
+    return torch.cat([torch.cos(t / 2), k * rotvec], dim=-1)
+
+
+@torch.no_grad()
+def rotate_joint(edit, joint, axis, angle, translation=None, num_joints=None):
+    """:296-321 — the edit ``{'local_rotation': (J, 4), 'global_trans': (1, 3)}`` with row ``joint`` OVERWRITTEN (not composed) by
+    the wxyz quaternion of the rotation vector ``axis * angle`` and ``global_trans`` overwritten by ``translation`` (zeros if
+    None).  ``edit = None`` creates one of ``num_joints`` identity rows first, on ``axis``'s device (:313-317: the reference sizes
+    it by its skeleton); an existing edit is changed in place and returned.  ``joint`` and ``angle`` may be device scalars."""
+    if edit is None:
+        if num_joints is None:
+            raise ValueError("rotate_joint: a new edit needs num_joints")
+        axis = torch.as_tensor(axis, dtype=torch.float32)
+        q = torch.zeros(int(num_joints), 4, dtype=torch.float32, device=axis.device)
+        q[:, 0] = 1
+        edit = {"local_rotation": q, "global_trans": torch.zeros(1, 3, device=axis.device)}
+    q = edit["local_rotation"]
+    axis = torch.as_tensor(axis, dtype=q.dtype, device=q.device)
+    angle = torch.as_tensor(angle, dtype=q.dtype, device=q.device)
+    joint = torch.as_tensor(joint, device=q.device).long().reshape(1)
+    q.index_copy_(0, joint, rotvec_to_quaternion(axis * angle)[None])
+    if translation is None:
+        edit["global_trans"] = torch.zeros(1, 3, dtype=q.dtype, device=q.device)
+    else:
+        edit["global_trans"] = torch.as_tensor(translation, dtype=q.dtype, device=q.device).reshape(1, 3)
+    return edit
+
+
+def apply_edit(node_attrs, edit):
+    """:397-399 — the pose of the frame with the edit on it: ``local_rotation = quaternion_multiply(edit, pose)`` (the Hamilton
+    product, real part made non-negative as the reference's function does), ``global_trans`` summed.  A new dict; other keys are kept."""
+    out = dict(node_attrs)
+    if edit is not None:
+        out["local_rotation"] = quaternion_multiply(edit["local_rotation"], node_attrs["local_rotation"])
+        out["global_trans"] = node_attrs["global_trans"] + edit["global_trans"]
+    return out
+
+
+# --------------------------------------------------------------------------- inverse kinematics
+def rig_extent(joints):
+    """The largest axis range of the rest joints as a (1,) device tensor; 1 where it is 0 (one joint, or all in one place)."""
+    e = (joints.max(dim=0).values - joints.min(dim=0).values).max().reshape(1)
+    return torch.where(e > 0, e, torch.ones_like(e))
+
+
+def _rig(skeleton):
+    """(joints (J, 3) float32, parents (J,) int32 with 0 at the root) on the device."""
+    if isinstance(skeleton, (tuple, list)):
+        joints, parents = skeleton
+        joints = L.require_cuda_f32("joints", joints.detach(), (None, 3))
+        if not torch.is_tensor(parents) or not parents.is_cuda:  # host data: checked here (a device tensor is clamped by the kernel)
+            p = np.asarray(parents.cpu() if torch.is_tensor(parents) else parents).astype(np.int64).reshape(-1).copy()
+            if p.shape[0] != joints.shape[0]:
+                raise L.RiggsHipError("parents has %d entries for %d joints" % (p.shape[0], joints.shape[0]))
+            p[0] = 0
+            if (p[1:] >= np.arange(1, p.shape[0])).any() or (p < 0).any():
+                raise L.RiggsHipError("0 <= parents[i] < i is required (skeleton_warp.py:257-263)")
+            parents = torch.from_numpy(p)
+        parents = parents.to(joints.device, torch.int32).contiguous()
+        if parents.numel() != joints.shape[0]:
+            raise L.RiggsHipError("parents has %d entries for %d joints" % (parents.numel(), joints.shape[0]))
+        return joints, parents
+    joints = skeleton._joints()
+    return L.require_cuda_f32("joints", joints, (None, 3)), skeleton._parents_dev(joints.device)
+
+
+@torch.no_grad()
+def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterations=16, damping=None, max_step=None,
+             solve_translation=False):
+    """Turn the joints of ``pose`` so that the ``handles`` joints reach ``targets``; the chain follows.
+
+    ``skeleton``: a ``SkeletonWarp`` or ``(joints (J, 3), parents (J,))``, 1 <= J <= 256.  ``pose``: the dict ``deform_by_pose`` /
+    ``get_pose_info`` use — ``local_rotation`` (J, 4) or (B, J, 4), un-normalised wxyz; ``global_trans`` (1, 3) or (B, 3).
+    ``handles``: (E,) or (B, E) joint indices, 1 <= E <= 8; ``targets`` (..., E, 3); ``weights`` (..., E), a weight <= 0 switches
+    its handle off (so the number of live handles changes without a new shape); ``locked`` (J,) bool: joints that keep their
+    rotation.  Unbatched arguments are shared by the B problems.  ``damping`` (> 0) and ``max_step`` default to 0.05 and 0.5 times
+    ``rig_extent(joints)``, which stays on the device.  ``solve_translation``: ``global_trans`` is solved for as well.
+    Where a target may be out of reach, give a ``damping`` of about ``max_step``: with the small default the stretched chain
+    swings from iteration to iteration instead of settling (the method's behaviour, in float64 as well).
+
+    Returns ``{'local_rotation', 'global_trans', 'd_nodes', 'residual'}``: the pose (the input's shapes; it feeds
+    ``deform_by_pose``, ``deform_sequence`` and ``run_interpolation`` unchanged), the posed skeleton (..., J, 3) for
+    ``skeleton_overlay`` and ``|target - posed handle|`` (..., E).  The iteration is stated in include/riggs_hip.h.
+
+    One launch, allocations through torch only, nothing read back: the call can be captured in a ``torch.cuda.graph`` and
+    replayed after ``targets`` / ``handles`` / ``weights`` (device tensors) were changed in place.  Handle indices given on the
+    host (a list, an array, a CPU tensor) are checked here; on the device they are not read: the kernel switches off a handle
+    outside [0, J) and reports NaN as its residual."""
+    joints, parents = _rig(skeleton)
+    dev, J = joints.device, int(joints.shape[0])
+    if not 1 <= J <= MAX_JOINTS:
+        raise L.RiggsHipError("solve_ik: %d joints, 1 to %d are supported" % (J, MAX_JOINTS))
+    q = L.require_cuda_f32("local_rotation", pose["local_rotation"].detach())
+    if q.dim() not in (2, 3) or tuple(q.shape[-2:]) != (J, 4):
+        raise L.RiggsHipError("local_rotation has shape %s, expected (%d, 4) or (B, %d, 4)" % (tuple(q.shape), J, J))
+    gt = L.require_cuda_f32("global_trans", pose["global_trans"].detach())
+    if torch.is_tensor(handles) and handles.is_cuda:
+        h = handles
+    else:
+        h_host = np.asarray(handles.cpu() if torch.is_tensor(handles) else handles)
+        if h_host.size and (not np.issubdtype(h_host.dtype, np.integer) or h_host.min() < 0 or h_host.max() >= J):
+            raise L.RiggsHipError("solve_ik: a handle is no joint index in [0, %d)" % J)
+        h = torch.from_numpy(h_host.astype(np.int32)).to(dev)
+    if h.dim() not in (1, 2) or not 1 <= h.shape[-1] <= MAX_HANDLES:
+        raise L.RiggsHipError("solve_ik: handles has shape %s, expected (E,) or (B, E) with 1 <= E <= %d" % (tuple(h.shape), MAX_HANDLES))
+    E = int(h.shape[-1])
+    targets = L.require_cuda_f32("targets", targets.detach())
+    if targets.dim() not in (2, 3) or tuple(targets.shape[-2:]) != (E, 3):
+        raise L.RiggsHipError("targets has shape %s, expected (..., %d, 3)" % (tuple(targets.shape), E))
+    if weights is not None:
+        weights = L.require_cuda_f32("weights", weights.detach())
+        if weights.dim() not in (1, 2) or weights.shape[-1] != E:
+            raise L.RiggsHipError("weights has shape %s, expected (..., %d)" % (tuple(weights.shape), E))
+    if locked is not None:
+        locked = torch.as_tensor(locked).to(dev)
+        if tuple(locked.shape) != (J,):
+            raise L.RiggsHipError("locked has shape %s, expected (%d,)" % (tuple(locked.shape), J))
+        locked = (locked != 0).to(torch.uint8).contiguous()
+    if int(iterations) < 0:
+        raise L.RiggsHipError("solve_ik: iterations >= 0")
+    relative = 0
+    if damping is None:
+        damping, relative = 0.05, relative | 1
+    elif not float(damping) > 0:
+        raise L.RiggsHipError("solve_ik: damping must be > 0, got %r" % (damping,))
+    if max_step is None:
+        max_step, relative = 0.5, relative | 2
+    elif not float(max_step) >= 0:
+        raise L.RiggsHipError("solve_ik: max_step must be >= 0, got %r" % (max_step,))
+    extent = rig_extent(joints) if relative else None
+
+    # the batch: what has a leading dimension names B, the rest is shared
+    gt = gt.reshape(-1, 3)
+    batched = q.dim() == 3 or h.dim() == 2 or targets.dim() == 3 or (weights is not None and weights.dim() == 2) or gt.shape[0] > 1
+    sizes = {int(t.shape[0]) for t, d in ((q, 3), (h, 2), (targets, 3), (weights, 2), (gt, 2)) if t is not None and t.dim() == d}
+    sizes.discard(1)
+    if len(sizes) > 1:
+        raise L.RiggsHipError("solve_ik: the arguments name different batch sizes %s" % sorted(sizes))
+    B = sizes.pop() if sizes else 1
+    if gt.numel() not in (3, 3 * B):
+        raise L.RiggsHipError("global_trans has shape %s, expected (1, 3) or (%d, 3)" % (tuple(gt.shape), B))
+
+    def full(t, tail):  # (B, *tail) contiguous: a view where the tensor already is, so a graph replay sees in-place changes
+        return t.reshape((-1,) + tail).expand((B,) + tail).contiguous()
+    qb, gtb, hb, tb = full(q, (J, 4)), full(gt, (3,)), full(h.to(torch.int32), (E,)), full(targets, (E, 3))
+    wb = None if weights is None else full(weights, (E,))
+    f32 = dict(dtype=torch.float32, device=dev)
+    q_out, gt_out = torch.empty(B, J, 4, **f32), torch.empty(B, 3, **f32)
+    d_nodes, residual = torch.empty(B, J, 3, **f32), torch.empty(B, E, **f32)
+    with torch.cuda.device(dev):
+        L.check(L.lib().riggs_ik_solve(B, J, E, joints.data_ptr(), parents.data_ptr(), qb.data_ptr(), gtb.data_ptr(), hb.data_ptr(),
+                                       tb.data_ptr(), L.ptr(wb), L.ptr(locked), int(iterations), float(damping), float(max_step),
+                                       L.ptr(extent), relative, int(bool(solve_translation)), q_out.data_ptr(), gt_out.data_ptr(),
+                                       d_nodes.data_ptr(), residual.data_ptr(), L.stream_ptr()), "riggs_ik_solve")
+    if batched:
+        return {"local_rotation": q_out, "global_trans": gt_out, "d_nodes": d_nodes, "residual": residual}
+    return {"local_rotation": q_out[0], "global_trans": gt_out, "d_nodes": d_nodes[0], "residual": residual[0]}
