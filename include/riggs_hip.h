@@ -284,7 +284,10 @@ int riggs_lbs_forward(int32_t num_points, int32_t num_joints, int32_t K, const f
                       float* d_xyz, float* d_rotation, float* nn_weight, int64_t* nn_idx,
                       void* bone_table /* may be NULL; riggs_lbs_bone_table_bytes() of device scratch, see below */,
                       riggs_stream stream);
-/* bone_table (riggs_lbs_forward / riggs_lbs_forward_fk; may be NULL): device scratch of riggs_lbs_bone_table_bytes() bytes.  With
+/* bone_table (riggs_lbs_forward / riggs_lbs_forward_fk; may be NULL): device scratch of riggs_lbs_bone_table_bytes() bytes.  Given
+ * one, a forward over <= 64 joints always leaves its staged bone records there (segment, radius term, transform and rotation of
+ * every bone), whichever kernel runs: riggs_lbs_backward_table stages from them instead of building them again in every
+ * workgroup.  Results are bit-identical with and without a table, forward and backward.  Also, with
  * it the all-bones forward (K = -1, no weight_mod, no nn outputs) of a LARGE scene (>= 1 M Gaussians, >= 16 joints) reads the bone
  * records through the scalar cache as SGPR operands — a one-workgroup launch writes the table (and, in the _fk form, runs the
  * chain) in front — instead of staging them in every workgroup's LDS: 2 M x 64 joints 129 -> 104 us, results bit-identical.
@@ -312,6 +315,18 @@ int riggs_lbs_backward(int32_t num_points, int32_t num_joints, int32_t K, const 
                        float* dL_dweight_mod /* (N, J-1), required with weight_mod */,
                        void* workspace /* riggs_lbs_backward_workspace_bytes(N, J) */, riggs_stream stream);
 size_t riggs_lbs_backward_workspace_bytes(int32_t num_points, int32_t num_joints);
+/* The same backward with the bone table that the forward of the SAME inputs (joints, parents, node_radius_log, transforms,
+ * node_rot) filled: every workgroup copies the records with one coalesced read where riggs_lbs_backward rebuilds them (per bone
+ * two dependent loads, an exp and two divisions, in front of the walk).  bone_table NULL, or more than 64 joints: exactly
+ * riggs_lbs_backward.  Gradients are bit-identical to it wherever it is reproducible itself.  The table lives with what the
+ * forward saves for the backward and is read only.  (Added symbol: RIGGS_ABI_VERSION is unchanged.) */
+int riggs_lbs_backward_table(int32_t num_points, int32_t num_joints, int32_t K, const float* x, const float* joints,
+                             const int32_t* parents, const float* node_radius_log, const float* transforms,
+                             const float* node_rot, const float* global_trans, const float* motion_mask,
+                             const float* weight_mod, const float* g_xyz, const float* g_rot, float* dL_dtransforms,
+                             float* dL_dnode_radius_log, float* dL_dglobal_trans, float* dL_dmotion_mask,
+                             float* dL_dweight_mod, const void* bone_table /* may be NULL */,
+                             void* workspace /* riggs_lbs_backward_workspace_bytes(N, J) */, riggs_stream stream);
 
 /* ---- Playback of a pose track (inference only: no backward exists; riggs_amd/playback.py).  Added symbols: RIGGS_ABI_VERSION
  * is unchanged.

@@ -29,6 +29,13 @@ __device__ __forceinline__ int rect_tile(const ushort4 rc, int l, int grid_x) {
   return (rc.y + ry) * grid_x + rc.x + rx;
 }
 
+// (one 8-byte load: left to itself the compiler reads a rectangle field by field where an early exit tests two of them first —
+// two dependent round trips)
+__device__ __forceinline__ ushort4 unpack_rect(const uint2 w) {
+  return make_ushort4((unsigned short)(w.x & 0xFFFFu), (unsigned short)(w.x >> 16), (unsigned short)(w.y & 0xFFFFu), (unsigned short)(w.y >> 16));
+}
+__device__ __forceinline__ ushort4 load_rect(const ushort4* p) { return unpack_rect(*reinterpret_cast<const uint2*>(p)); }
+
 __global__ __launch_bounds__(1024) void bin_count_kernel(int N, int T, int grid_x, int g_per_block,
                                                         const uint32_t* __restrict__ order,
                                                         const ushort4* __restrict__ rect,
@@ -43,7 +50,7 @@ __global__ __launch_bounds__(1024) void bin_count_kernel(int N, int T, int grid_
     const uint32_t g = order[s];
     // (the one gather of the rectangles by depth order — a 64-byte line per Gaussian for 8 bytes; the scatter kernel reads
     // this sorted copy, coalesced.  A culled Gaussian's rectangle is empty: preprocess_fwd writes it for every Gaussian)
-    const ushort4 rc = rect[g];
+    const ushort4 rc = load_rect(rect + g);
     srect[s] = rc;
     if (rc.z == rc.x) continue;
     for (int y = rc.y; y < rc.w; y++)
@@ -282,8 +289,6 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
   unsigned short* s_rel = reinterpret_cast<unsigned short*>(s_mem + T);  // [W][Tpad]
   uint32_t* s_rel32 = s_mem + T;                                        // same storage as packed pairs
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int e = tid; e < W * (Tpad >> 1); e += blockDim.x) s_rel32[e] = 0u;
-  __syncthreads();
   // a wave walks g_per_wave Gaussians in batches of 64 (one batch in the headline configuration; more when N is large,
   // so that the O(T) set-up of a workgroup — cursor tables, tile bases, its row of the chunk table — is paid per thousands
   // of Gaussians and the chunk table stays small: bin_plan)
@@ -298,14 +303,31 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
       n = (uint32_t)((int)(rc.z - rc.x) * (int)(rc.w - rc.y));
     }
   };
+  // Every global load that the kernel's head needs is asked for HERE, in one round trip: the wave's first batch (it stays in
+  // registers for the walk below) and, behind it, the tile counts and the chunk's table row of the scan's first four rounds —
+  // all of them up to 4 x blockDim tiles.  Asked for where they are used, behind the barrier of phase (i), the counts and the
+  // row were a second exposed round trip; the compiler keeps loads where it finds them, and waits for everything in flight at
+  // the head of the histogram loop, so the batch goes first and nothing is computed from it before the others are under way.
+  uint32_t nx_g = 0u;
+  uint2 nx_w = make_uint2(0u, 0u);  // (unpacked behind the barrier: a field taken here would wait for the load here)
+  if (first + lane < end) { nx_g = order[first + lane]; nx_w = *reinterpret_cast<const uint2*>(srect + first + lane); }
+  const uint32_t* row = table + (size_t)blockIdx.x * T;
+  uint32_t cq0[4], rq0[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int t = k * (int)blockDim.x + tid;
+    cq0[k] = (t < T) ? tile_count[t] : 0u;
+    rq0[k] = (t < T) ? row[t] : 0u;
+  }
+  for (int e = tid; e < W * (Tpad >> 1); e += blockDim.x) s_rel32[e] = 0u;
+  __syncthreads();
+  ushort4 nx_rc = unpack_rect(nx_w);
+  uint32_t nx_n = (uint32_t)((int)(nx_rc.z - nx_rc.x) * (int)(nx_rc.w - nx_rc.y));  // (an absent Gaussian's rectangle is empty)
   // (i) per-wave tile histogram (16-bit counters packed in pairs; a wave adds at most g_per_wave <= 1024 per tile)
-  uint32_t nx_g = 0u, nx_n = 0u;          // the first batch stays in registers for the walk below
-  ushort4 nx_rc = make_ushort4(0, 0, 0, 0);
   for (int s0 = first; s0 < end; s0 += 64) {
-    uint32_t g, n;
-    ushort4 rc;
-    load_batch(s0, g, n, rc);
-    if (s0 == first) { nx_g = g; nx_n = n; nx_rc = rc; }
+    uint32_t g = nx_g, n = nx_n;
+    ushort4 rc = nx_rc;
+    if (s0 != first) load_batch(s0, g, n, rc);
     if (n) {
       uint32_t* hist = s_rel32 + (size_t)wave * (Tpad >> 1);
       for (int y = rc.y; y < rc.w; y++)
@@ -319,7 +341,6 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
   // (ii) counts -> offsets of the waves inside the block's segment; absolute base of the segment = start of the tile's
   // list (every workgroup scans the tile counts itself: T words from L2, instead of a launch that does it once) + the
   // instances of the earlier chunks
-  const uint32_t* row = table + (size_t)blockIdx.x * T;
   {
     __shared__ uint32_t s_wsum[16];
     __shared__ uint32_t s_run;
@@ -332,6 +353,7 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int t = base0 + k * (int)blockDim.x + tid;
+        if (base0 == 0) { cq[k] = cq0[k]; rq[k] = rq0[k]; continue; }  // (in registers since the kernel's entry)
         cq[k] = (t < T) ? tile_count[t] : 0u;
         rq[k] = (t < T) ? row[t] : 0u;
       }
@@ -537,7 +559,7 @@ __global__ __launch_bounds__(1024) void gbin_count_kernel(int N, int T, int G, i
     const int s = s0 + lane;
     if (s < end) {
       const uint32_t g = order[s];
-      const ushort4 rc = rect[g];
+      const ushort4 rc = load_rect(rect + g);
       srect[s] = rc;  // (the rectangles in depth order: see bin_count_kernel)
       if (rc.z > rc.x) {
         for (int y = rc.y; y < rc.w; y++)
@@ -1178,12 +1200,18 @@ __global__ __launch_bounds__(CHUNK / 8) void rs_count_kernel(int N, int pass, Rs
   const uint2* src; uint2* dst;
   rs_route(bufs, pass, three, src, dst);
   const int shift = pass * RS_BITS;
+  if (src) {
+    // (the later passes: all of the thread's keys in one round trip, at clamped indices — read where they are counted, each load
+    // stood in front of its own LDS atomic: eight dependent round trips)
+#pragma unroll
+    for (int k = 0; k < CHUNK / NT; k++) k0[k] = src[min(first + k * NT + (int)threadIdx.x, N - 1)].x;
+  }
   for (int b = threadIdx.x; b < RS_BINS; b += NT) s_hist[b] = 0u;
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < CHUNK / NT; k++) {
     const int i = first + k * NT + threadIdx.x;
-    if (i < N) atomicAdd(&s_hist[((src ? src[i].x : k0[k]) >> shift) & (RS_BINS - 1)], 1u);
+    if (i < N) atomicAdd(&s_hist[(k0[k] >> shift) & (RS_BINS - 1)], 1u);
   }
   __syncthreads();
   uint32_t* row = table + (size_t)blockIdx.x * RS_BINS;
@@ -1340,29 +1368,38 @@ __global__ __launch_bounds__(RS_SC_WAVES * 64) void rs_scatter_kernel(int N, int
   const int shift = pass * RS_BITS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NT = RS_SC_WAVES * 64, PER = RS_BINS / NT;   // bins per thread in the scan
-  // every global load of the workgroup up front — its elements, its row of the chunk table, the bin totals — so that the
+  // every global load of the workgroup up front — its row of the chunk table, the bin totals, its elements — so that the
   // scan and the two barriers below run under ONE round trip instead of in front of two more (the compiler keeps loads
-  // behind a barrier where it finds them)
+  // behind a barrier where it finds them).  The row and the totals first: where the two sources' paths join, the compiler
+  // waits for all that is in flight.
   constexpr int STEPS = CHUNK / NT;
   const int wfirst = blockIdx.x * CHUNK + wave * (64 * STEPS);
-  uint32_t key[STEPS], val[STEPS];
-#pragma unroll
-  for (int st = 0; st < STEPS; st++) {
-    const int i = wfirst + st * 64 + lane;
-    key[st] = 0u; val[st] = 0u;
-    if (i < N) {
-      if (src) { const uint2 kv = src[i]; key[st] = kv.x; val[st] = kv.y; }
-      else { key[st] = bufs.k_in[i]; val[st] = (uint32_t)i; }
-    }
-  }
   const uint32_t* row = table + (size_t)blockIdx.x * RS_BINS;
   uint32_t rw[PER];
 #pragma unroll
   for (int k = 0; k < PER; k++) rw[k] = row[tid * PER + k];
-  // exclusive scan of bin_count
   uint32_t c[PER], tsum = 0;
 #pragma unroll
-  for (int k = 0; k < PER; k++) { c[k] = bin_count[tid * PER + k]; tsum += c[k]; }
+  for (int k = 0; k < PER; k++) c[k] = bin_count[tid * PER + k];
+  // (plain loads at clamped indices, one source per loop: a lane behind the end reads the last element and never uses it.  Written
+  // as "if (i < N) { if (src) .. else .. }" per step, every load was followed by a wait for it — STEPS dependent round trips)
+  uint32_t key[STEPS], val[STEPS];
+  if (src) {
+#pragma unroll
+    for (int st = 0; st < STEPS; st++) {
+      const uint2 kv = src[min(wfirst + st * 64 + lane, N - 1)];
+      key[st] = kv.x; val[st] = kv.y;
+    }
+  } else {
+#pragma unroll
+    for (int st = 0; st < STEPS; st++) {
+      const int i = wfirst + st * 64 + lane;
+      key[st] = bufs.k_in[min(i, N - 1)]; val[st] = (uint32_t)i;
+    }
+  }
+  // exclusive scan of bin_count
+#pragma unroll
+  for (int k = 0; k < PER; k++) tsum += c[k];
   uint32_t v = tsum;
   for (int o = 1; o < 64; o <<= 1) {
     const uint32_t u = (uint32_t)__shfl_up((int)v, o);

@@ -98,11 +98,26 @@ struct LbsArgs {
   const float* local_rot;
   float *fk_transforms, *fk_node_rot, *fk_d_nodes;
   int mod_lds;  // forward: weight_mod is staged through LDS (the launch reserved the tile)
+  // the caller's bone table (<= 64 joints; struct Bone below): the forward's workgroup 0 leaves its staged records there, the
+  // backward stages from them — one coalesced read instead of building every record again in every workgroup
+  Bone* table_out;
+  const Bone* table_in;
 };
 
 // (transforms / node_rot: global memory, or the LDS arrays of a kinematic chain that this workgroup ran itself)
 __device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones, const float* transforms, const float* node_rot);
-__device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones) { stage_bones(a, bones, a.transforms, a.node_rot); }
+// (the backward, given the forward's table: the records as the forward staged them — bone_geometry's two dependent loads, exp and
+// divisions, and the gather of G and q, are not repeated; sizeof(Bone) is a multiple of 16)
+__device__ __forceinline__ void stage_bones(const LbsArgs& a, Bone* bones) {
+  if (a.table_in) {
+    const float4* src = reinterpret_cast<const float4*>(a.table_in);
+    float4* dst = reinterpret_cast<float4*>(bones);
+    for (int e = threadIdx.x; e < (a.J - 1) * (int)(sizeof(Bone) / 16); e += blockDim.x) dst[e] = src[e];
+    __syncthreads();
+    return;
+  }
+  stage_bones(a, bones, a.transforms, a.node_rot);
+}
 // the part of bone k's record that no pose changes: the segment, its clamped squared length, 1 / (2 r^2)
 __device__ __forceinline__ void bone_geometry(const LbsArgs& a, int k, Bone& b) {
   const int child = k + 1, par = a.parents[child];
@@ -299,6 +314,10 @@ __global__ __launch_bounds__(256) void lbs_forward_kernel(LbsArgs a) {
     stage_bones(a, bones, &G[0][0], &Q[0][0]);
   } else {
     stage_bones(a, bones);
+  }
+  if constexpr (!WIDE) {
+    // (the staged records for the backward, when the caller handed over a table)
+    if (a.table_out && blockIdx.x == 0) for (int k = threadIdx.x; k < a.J - 1; k += 256) a.table_out[k] = bones[k];
   }
   // PTS Gaussians per thread (all-bones configuration): what bounds this loop at 64 joints is the LDS handing every wave the
   // bone records (24 floats per bone, broadcast: 8 cycles of the CU's 128 B / clk return path per ds_read_b128 and wave,
@@ -605,8 +624,10 @@ __device__ __forceinline__ void lbs_bonelane_prologue(const LbsArgs& a, Bone* bo
 template <int NBLK, bool MOD, int GPB>
 __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
   __shared__ Bone bones[MAX_J - 1 + LB_BONES];
-  __shared__ float s_acc[MAX_J - 1 + LB_BONES][13];
-  __shared__ float s_gt[3];
+  // (a slot per wave: the four waves' sums meet in wave order, so the workgroup's partial — and with the fixed-order second stage
+  // every gradient of the call — is the same to the bit from run to run)
+  __shared__ float s_acc[4][MAX_J - 1 + LB_BONES][13];
+  __shared__ float s_gt[4][3];
   const int B = a.J - 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slot = lane >> 3, bl = lane & 7;
@@ -636,7 +657,7 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
     }
   };
   request(0);
-  lbs_bonelane_prologue(a, bones, s_acc, s_gt, NBLK);
+  lbs_bonelane_prologue(a, bones, s_acc[0], s_gt[0], NBLK);
   float acc[NBLK][13];
 #pragma unroll
   for (int bb = 0; bb < NBLK; bb++)
@@ -762,25 +783,27 @@ __global__ __launch_bounds__(256) void lbs_backward_bonelane_kernel(LbsArgs a) {
     if (bl == 0) { gt0 += gh0; gt1 += gh1; gt2 += gh2; }
   }
   }
-  // fold the 8 slot rows (lanes l, l^8, l^16, l^32) and push to the workgroup accumulators
+  // fold the 8 slot rows (lanes l, l^8, l^16, l^32) and leave them in the wave's slot of the workgroup accumulators (a wave
+  // writes every entry of its slot, zeros where it walked nothing)
 #pragma unroll
   for (int bb = 0; bb < NBLK; bb++)
 #pragma unroll
     for (int e = 0; e < 13; e++) {
       float t = acc[bb][e];
       t += __shfl_xor(t, 8); t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
-      if (slot == 0) atomicAdd(&s_acc[bb * LB_BONES + bl][e], t);
+      if (slot == 0) s_acc[wave][bb * LB_BONES + bl][e] = t;
     }
   gt0 = wave_sum(gt0); gt1 = wave_sum(gt1); gt2 = wave_sum(gt2);
-  if (lane == 63) { atomicAdd(&s_gt[0], gt0); atomicAdd(&s_gt[1], gt1); atomicAdd(&s_gt[2], gt2); }
+  if (lane == 63) { s_gt[wave][0] = gt0; s_gt[wave][1] = gt1; s_gt[wave][2] = gt2; }
   __syncthreads();
-  // per-workgroup partial sums; lbs_backward_finish_kernel adds them up in a fixed order.  (The partial itself is not
-  // run-to-run reproducible to the bit: the workgroup's four waves add into s_acc / s_gt with LDS atomics in the order they
-  // arrive, so from three contributing waves on (N > 512) the last place of dG / drho / dgt depends on timing — measured on
-  // the MI355X, NOTES.md.  A fixed order here would need a slot per wave in LDS.)
+  // per-workgroup partial sums: the waves' slots added in wave order (as the LDS atomics that used to meet here did when the waves
+  // arrived in that order; in any other order the last place of dG / drho / dgt differed from run to run from three contributing
+  // waves on — N > 512); lbs_backward_finish_kernel adds the partials up in a fixed order too
   float* part = a.partial + (size_t)blockIdx.x * (B * 13 + 3);
-  for (int e = threadIdx.x; e < B * 13; e += 256) part[e] = (&s_acc[0][0])[e];
-  if (threadIdx.x < 3) part[B * 13 + threadIdx.x] = s_gt[threadIdx.x];
+  for (int e = threadIdx.x; e < B * 13; e += 256)
+    part[e] = (((0.f + (&s_acc[0][0][0])[e]) + (&s_acc[1][0][0])[e]) + (&s_acc[2][0][0])[e]) + (&s_acc[3][0][0])[e];
+  if (threadIdx.x < 3)
+    part[B * 13 + threadIdx.x] = (((0.f + s_gt[0][threadIdx.x]) + s_gt[1][threadIdx.x]) + s_gt[2][threadIdx.x]) + s_gt[3][threadIdx.x];
 }
 
 // one workgroup per output value: sum over the workgroups' partials
@@ -1437,6 +1460,7 @@ static int launch_lbs_forward(LbsArgs& a, void* bone_table, hipStream_t s) {
     else hipLaunchKernelGGL((lbs_forward_scalar_kernel<1>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a, table);
   } else {
     ProfScope ps(PROF_LBS_FWD, s);
+    a.table_out = (Bone*)bone_table;  // (may be NULL)
     if (a.K > 0) hipLaunchKernelGGL((lbs_forward_kernel<true, FK, 1>), dim3(lbs_grid(N, 1)), dim3(256), 0, s, a);
     else if (lbs_two_per_thread(N, J)) hipLaunchKernelGGL((lbs_forward_kernel<false, FK, 2>), dim3(lbs_grid(N, 2)), dim3(256), 0, s, a);
     else { const size_t lds = lbs_mod_lds(a, 1); hipLaunchKernelGGL((lbs_forward_kernel<false, FK, 1>), dim3(lbs_grid(N, 1)), dim3(256), lds, s, a); }
@@ -1526,12 +1550,24 @@ int riggs_lbs_backward(int32_t N, int32_t J, int32_t K, const float* x, const fl
                        const float* g_xyz, const float* g_rot, float* dL_dtransforms, float* dL_dnode_radius_log,
                        float* dL_dglobal_trans, float* dL_dmotion_mask, float* dL_dweight_mod, void* workspace,
                        riggs_stream stream) {
+  return riggs_lbs_backward_table(N, J, K, x, joints, parents, node_radius_log, transforms, node_rot, global_trans, motion_mask,
+                                  weight_mod, g_xyz, g_rot, dL_dtransforms, dL_dnode_radius_log, dL_dglobal_trans, dL_dmotion_mask,
+                                  dL_dweight_mod, nullptr, workspace, stream);
+}
+
+int riggs_lbs_backward_table(int32_t N, int32_t J, int32_t K, const float* x, const float* joints, const int32_t* parents,
+                             const float* node_radius_log, const float* transforms, const float* node_rot,
+                             const float* global_trans, const float* motion_mask, const float* weight_mod,
+                             const float* g_xyz, const float* g_rot, float* dL_dtransforms, float* dL_dnode_radius_log,
+                             float* dL_dglobal_trans, float* dL_dmotion_mask, float* dL_dweight_mod, const void* bone_table,
+                             void* workspace, riggs_stream stream) {
   LbsArgs a;
   int rc = fill_lbs(a, N, J, K, x, joints, parents, node_radius_log, transforms, node_rot, global_trans, motion_mask);
   if (rc) return rc;
   a.g_xyz = g_xyz; a.g_rot = g_rot; a.dG = dL_dtransforms; a.drho = dL_dnode_radius_log; a.dgt = dL_dglobal_trans;
   a.dmask = dL_dmotion_mask;
   a.weight_mod = weight_mod; a.dmod = dL_dweight_mod;
+  a.table_in = J <= MAX_J ? (const Bone*)bone_table : nullptr;  // (skeletons of more joints never wrote one)
   RIGGS_REQUIRE(weight_mod == nullptr || (K <= 0 && dL_dweight_mod != nullptr), "weight_mod needs K = -1 and dL_dweight_mod");
   a.partial = (float*)workspace;
   RIGGS_REQUIRE(workspace != nullptr, "riggs_lbs_backward needs its workspace");

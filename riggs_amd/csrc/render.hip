@@ -797,13 +797,13 @@ __global__ __launch_bounds__(64 * NW) void render_bwd_kernel(RenderBwdArgs a) {
     float4 xy, co, cc, acc;
     float Tn, g0, g1, g2, gD, gA, Ts, S0, S1, S2, Ds;
   };
-  auto issue_level3 = [&](const u4v wk, uint32_t id, uint32_t n, Level3& r) {
-    const int tile = (int)wk.x, pos0 = (int)wk.y * 64;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    r.xy = z; r.co = z; r.cc = z; r.acc = z;
+  // (the two halves of level 3.  The pixel's state hangs off the work entry alone — `want` only spares the traffic of the pixels
+  // that this chunk lies behind, which stage_pixels drops whatever was loaded —, the records off the list entry)
+  auto issue_pixel_state = [&](const u4v wk, bool want, Level3& r) {
+    const int tile = (int)wk.x;
+    r.acc = make_float4(0.f, 0.f, 0.f, 0.f);
     r.Tn = 0.f; r.g0 = 0.f; r.g1 = 0.f; r.g2 = 0.f; r.gD = 0.f; r.gA = 0.f; r.Ts = 1.f; r.S0 = 0.f; r.S1 = 0.f; r.S2 = 0.f; r.Ds = 0.f;
-    if (pos0 + lane < (int)wk.w) { r.xy = a.xyd[id]; r.co = a.conic_o[id]; r.cc = a.rgb[id]; }
-    if ((int)n > pos0) {  // (n is 0 for the lanes without a pixel and for the pixels outside the image)
+    if (want) {
       const int pxi = (tile % gx) * RIGGS_TILE + (spix & 15), pyi = (tile / gx) * RIGGS_TILE + (spix >> 4);
       const size_t pid = (size_t)pyi * a.W + pxi;
       const float* ck = a.ckpt + ((size_t)((wk.z >> 6) + wk.x + wk.y) * 5) * 256;
@@ -814,6 +814,15 @@ __global__ __launch_bounds__(64 * NW) void render_bwd_kernel(RenderBwdArgs a) {
       r.gA = a.dL_dalpha ? a.dL_dalpha[pid] : 0.f;
       r.Ts = ck[spix]; r.S0 = ck[256 + spix]; r.S1 = ck[512 + spix]; r.S2 = ck[768 + spix]; r.Ds = ck[1024 + spix];
     }
+  };
+  auto issue_records = [&](const u4v wk, uint32_t id, Level3& r) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    r.xy = z; r.co = z; r.cc = z;
+    if ((int)wk.y * 64 + lane < (int)wk.w) { r.xy = a.xyd[id]; r.co = a.conic_o[id]; r.cc = a.rgb[id]; }
+  };
+  auto issue_level3 = [&](const u4v wk, uint32_t id, uint32_t n, Level3& r) {
+    issue_records(wk, id, r);
+    issue_pixel_state(wk, (int)n > (int)wk.y * 64, r);  // (n is 0 for the lanes without a pixel and for the pixels outside the image)
   };
   auto stage_pixels = [&](const u4v wk, uint32_t n, const Level3& r) {  // this wave's pixels (one per lane) -> LDS
     const int pos0 = (int)wk.y * 64;
@@ -846,10 +855,17 @@ __global__ __launch_bounds__(64 * NW) void render_bwd_kernel(RenderBwdArgs a) {
   if (blockIdx.x < n_chunks) {
     wk_a = work[blockIdx.x];
     fetch_level2(wk_a, id_a, n_a);
+    // (the workgroup's first chunk has nobody in front to pipeline it: its pixels' state is asked for with the list entry, for
+    // every pixel of the image instead of only those that n_contrib admits, so that the prologue stands through two round trips
+    // behind the work entry instead of three; the guard stays in stage_pixels)
+    Level3 r;
+    {
+      const int pxi = ((int)wk_a.x % gx) * RIGGS_TILE + (spix & 15), pyi = ((int)wk_a.x / gx) * RIGGS_TILE + (spix >> 4);
+      issue_pixel_state(wk_a, lane < PPW && pxi < a.W && pyi < a.H, r);
+    }
     if (blockIdx.x + stride < n_chunks) { wk_b = work[blockIdx.x + stride]; fetch_level2(wk_b, id_b, n_b); }
     if (blockIdx.x + 2 * stride < n_chunks) wk_c = work[blockIdx.x + 2 * stride];
-    Level3 r;
-    issue_level3(wk_a, id_a, n_a, r);
+    issue_records(wk_a, id_a, r);
     stage_pixels(wk_a, n_a, r);
     xy = r.xy; co = r.co; cc = r.cc;
   }

@@ -103,7 +103,7 @@ struct PoseDeformFn : public torch::autograd::Function<PoseDeformFn> {
                                d_nodes.data_ptr<float>(), d_xyz.data_ptr<float>(), d_rot.data_ptr<float>(), ptr(bone_table), st),
           "riggs_lbs_forward_fk");
     variable_list saved = {acts, local_rot, global_trans, rho, mflat, x, joints, parents, transforms, node_rot, weight_mod,
-                           opt(fixed_coef), opt(fixed_loss), opt(sync)};
+                           opt(fixed_coef), opt(fixed_loss), opt(sync), opt(bone_table)};  // (the table: what the backward stages its bones from)
     for (auto& p : params) saved.push_back(p);
     ctx->save_for_backward(saved);
     ctx->saved_data["cfg"] = std::vector<int64_t>{depth, width, multires, skip, n_rot, K};
@@ -117,10 +117,10 @@ struct PoseDeformFn : public torch::autograd::Function<PoseDeformFn> {
     const auto s = ctx->get_saved_variables();
     const Tensor &acts = s[0], &local_rot = s[1], &global_trans = s[2], &rho = s[3], &mflat = s[4], &x = s[5], &joints = s[6],
                  &parents = s[7], &transforms = s[8], &node_rot = s[9], &weight_mod = s[10], &fixed_coef = s[11], &fixed_loss = s[12],
-                 &sync = s[13];
+                 &sync = s[13], &bone_table = s[14];
     const auto cfg = ctx->saved_data["cfg"].toIntVector();
     const int64_t depth = cfg[0], width = cfg[1], multires = cfg[2], skip = cfg[3], n_rot = cfg[4], K = cfg[5];
-    std::vector<Tensor> params(s.begin() + 14, s.end());
+    std::vector<Tensor> params(s.begin() + 15, s.end());
     const int64_t N = x.size(0), J = joints.size(0);
     const auto fo = x.options();
     Tensor g_xyz = g[0].defined() ? g[0].contiguous() : at::zeros({N, 3}, fo);
@@ -134,12 +134,12 @@ struct PoseDeformFn : public torch::autograd::Function<PoseDeformFn> {
     Tensor dmod = weight_mod.defined() ? at::empty({N, J - 1}, fo) : Tensor();
     riggs_stream st = current_stream(x);
     Tensor ws = at::empty({(int64_t)riggs_lbs_backward_workspace_bytes((int32_t)N, (int32_t)J)}, fo.dtype(at::kByte));
-    check(riggs_lbs_backward((int32_t)N, (int32_t)J, (int32_t)K, x.data_ptr<float>(), joints.data_ptr<float>(), parents.data_ptr<int32_t>(),
-                             rho.data_ptr<float>(), transforms.data_ptr<float>(), node_rot.data_ptr<float>(), global_trans.data_ptr<float>(),
-                             (const float*)ptr(mflat), (const float*)ptr(weight_mod), g_xyz.data_ptr<float>(), g_rot.data_ptr<float>(),
-                             dG.data_ptr<float>(), drho.data_ptr<float>(), dgt.data_ptr<float>(), (float*)ptr(dmask), (float*)ptr(dmod),
-                             ws.data_ptr(), st),
-          "riggs_lbs_backward");
+    check(riggs_lbs_backward_table((int32_t)N, (int32_t)J, (int32_t)K, x.data_ptr<float>(), joints.data_ptr<float>(),
+                                   parents.data_ptr<int32_t>(), rho.data_ptr<float>(), transforms.data_ptr<float>(), node_rot.data_ptr<float>(),
+                                   global_trans.data_ptr<float>(), (const float*)ptr(mflat), (const float*)ptr(weight_mod),
+                                   g_xyz.data_ptr<float>(), g_rot.data_ptr<float>(), dG.data_ptr<float>(), drho.data_ptr<float>(),
+                                   dgt.data_ptr<float>(), (float*)ptr(dmask), (float*)ptr(dmod), ptr(bone_table), ws.data_ptr(), st),
+          "riggs_lbs_backward_table");
     if (g[5].defined()) dG = at::add(dG, g[5]);
     if (g[4].defined()) dgt = at::add(dgt, g[4].reshape({-1}));
     Tensor gn = g[2].defined() ? g[2].contiguous() : Tensor();

@@ -316,20 +316,28 @@ def fk_forward(local_rot, joints, parents_i32, global_trans):
     return transforms, node_rot, d_nodes
 
 
-_LBS_TABLE_MIN_N = 1_000_000  # (csrc/deform.hip: LBS_PTS2_MIN_N — below it the library keeps the bone records in LDS anyway)
+_BONE_TABLE_MAX_J = 64  # (csrc/deform.hip: MAX_J — the table is a <= 64-joint form; beyond, the kernels never touch one)
+_BONE_TABLE_BYTES = []
 
 
-def _bone_table(N: int, device):
-    """Scratch for the skinning forward's bone table (``riggs_lbs_bone_table_bytes``; include/riggs_hip.h: bone_table) — handed
-    over for the scenes large enough for the library to use it, or whenever ``riggs_set_option("lbs_scalar", 1)`` asks for the form.
+def _bone_table_bytes() -> int:
+    if not _BONE_TABLE_BYTES:
+        _BONE_TABLE_BYTES.append(int(L.lib().riggs_lbs_bone_table_bytes()))
+    return _BONE_TABLE_BYTES[0]
+
+
+def _bone_table(J: int, device):
+    """The skinning forward's bone table (``riggs_lbs_bone_table_bytes``; include/riggs_hip.h: bone_table): the forward leaves its
+    staged bone records there and the backward stages from them (``riggs_lbs_backward_table``), so the table is saved with the
+    forward's other outputs; a large scene's forward also reads its records from it.  None beyond 64 joints.
     A fresh tensor per call: stream-ordered like every other buffer of the call, owned by the graph when captured."""
-    if N < _LBS_TABLE_MIN_N and L.OPTIONS_SET.get("lbs_scalar", 0) <= 0:
+    if J > _BONE_TABLE_MAX_J:
         return None
-    return torch.empty(int(L.lib().riggs_lbs_bone_table_bytes()), dtype=torch.uint8, device=device)
+    return torch.empty(_bone_table_bytes(), dtype=torch.uint8, device=device)
 
 
 def lbs_forward(x, joints, parents_i32, rho, transforms, node_rot, global_trans, mask, K=-1, want_weights=False,
-                weight_mod=None):
+                weight_mod=None, bone_table=None):
     N, J = x.shape[0], joints.shape[0]
     f32 = dict(dtype=torch.float32, device=x.device)
     d_xyz = torch.empty(N, 3, **f32)
@@ -337,10 +345,12 @@ def lbs_forward(x, joints, parents_i32, rho, transforms, node_rot, global_trans,
     Kp = K if K > 0 else J - 1
     w = torch.empty(N, Kp, **f32) if want_weights else None
     idx = torch.empty(N, Kp, dtype=torch.int64, device=x.device) if want_weights else None
+    if bone_table is None:  # (a caller that runs a backward hands over the table it will save)
+        bone_table = _bone_table(J, x.device)
     L.check(L.lib().riggs_lbs_forward(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
                                       transforms.data_ptr(), node_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mask),
                                       L.ptr(weight_mod), d_xyz.data_ptr(), d_rot.data_ptr(), L.ptr(w), L.ptr(idx),
-                                      L.ptr(_bone_table(N, x.device)), L.stream_ptr()),
+                                      L.ptr(bone_table), L.stream_ptr()),
             "riggs_lbs_forward")
     return d_xyz, d_rot, w, idx
 
@@ -358,9 +368,10 @@ class _DeformByPose(torch.autograd.Function):
         rho = L.require_cuda_f32("_node_radius", rho, (joints.shape[0],))
         mflat = None if mask is None else L.require_cuda_f32("motion_mask", mask.reshape(-1), (x.shape[0],))
         transforms, node_rot, d_nodes = fk_forward(local_rot, joints, parents_i32, global_trans)
+        table = _bone_table(joints.shape[0], x.device)
         d_xyz, d_rot, _, _ = lbs_forward(x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat, K,
-                                         weight_mod=weight_mod)
-        ctx.save_for_backward(local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod)
+                                         weight_mod=weight_mod, bone_table=table)
+        ctx.save_for_backward(local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod, table)
         ctx.K = K
         ctx.mask_shape = None if mask is None else mask.shape
         ctx.mark_non_differentiable(node_rot)
@@ -368,12 +379,13 @@ class _DeformByPose(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_rot, g_nodes, g_transforms, _g_node_rot):
-        local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod = ctx.saved_tensors
+        local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod, table = ctx.saved_tensors
         J = joints.shape[0]
         f32 = dict(dtype=torch.float32, device=x.device)
         dG, dgt = torch.empty(J, 12, **f32), torch.empty(3, **f32)
         dG, drho, dmask, dmod = _skinning_backward(ctx.K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat,
-                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[3])
+                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[3],
+                                                   bone_table=table)
         dq = torch.empty(J, 4, **f32)
         gn = None if g_nodes is None else g_nodes.contiguous()
         L.check(L.lib().riggs_fk_backward(J, local_rot.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), dG.data_ptr(),
@@ -383,8 +395,8 @@ class _DeformByPose(torch.autograd.Function):
 
 
 def _skinning_backward(K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat, weight_mod, g_xyz, g_rot,
-                       g_transforms, dG, dgt, want_mask):
-    """riggs_lbs_backward for _DeformByPose and _PoseDeform: fills the caller's ``dG`` (J, 12) and ``dgt`` (3,); returns
+                       g_transforms, dG, dgt, want_mask, bone_table=None):
+    """riggs_lbs_backward_table (``bone_table``: the one the forward filled, or None) for _DeformByPose and _PoseDeform: fills the caller's ``dG`` (J, 12) and ``dgt`` (3,); returns
     (dG + g_transforms where the returned transforms have a cotangent, drho — the gradient bucket's own range when one is
     registered —, dmask (N,) or None, dmod (N, J - 1) or None).  A missing cotangent of d_xyz / d_rotation counts as zeros."""
     N, J = x.shape[0], joints.shape[0]
@@ -397,10 +409,11 @@ def _skinning_backward(K, x, joints, parents_i32, rho, transforms, node_rot, glo
     dmod = torch.empty(N, J - 1, **f32) if weight_mod is not None else None
     lib = L.lib()
     ws = torch.empty(lib.riggs_lbs_backward_workspace_bytes(N, J), dtype=torch.uint8, device=x.device)
-    L.check(lib.riggs_lbs_backward(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
-                                   transforms.data_ptr(), node_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat),
-                                   L.ptr(weight_mod), g_xyz.data_ptr(), g_rot.data_ptr(), dG.data_ptr(), drho.data_ptr(),
-                                   dgt.data_ptr(), L.ptr(dmask), L.ptr(dmod), ws.data_ptr(), L.stream_ptr()), "riggs_lbs_backward")
+    L.check(lib.riggs_lbs_backward_table(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
+                                         transforms.data_ptr(), node_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat),
+                                         L.ptr(weight_mod), g_xyz.data_ptr(), g_rot.data_ptr(), dG.data_ptr(), drho.data_ptr(),
+                                         dgt.data_ptr(), L.ptr(dmask), L.ptr(dmod), L.ptr(bone_table), ws.data_ptr(),
+                                         L.stream_ptr()), "riggs_lbs_backward_table")
     if g_transforms is not None:
         dG = dG + g_transforms
     return dG, drho, dmask, dmod
@@ -435,9 +448,13 @@ class _PoseDeform(torch.autograd.Function):
         if n_acts is None:
             n_acts = _ACTS_FLOATS[key] = lib.riggs_pose_mlp_acts_floats(depth, width, multires)
         o_small = (n_acts + 63) & ~63
-        sbuf = torch.empty(o_small + _pose_block_floats(J), **f32)
+        # (the bone table behind the pose block, on a 256-byte boundary, in the same allocation)
+        o_table = o_small + ((_pose_block_floats(J) + 63) & ~63)
+        n_table = _bone_table_bytes() // 4 if J <= _BONE_TABLE_MAX_J else 0
+        sbuf = torch.empty(o_table + n_table, **f32)
         acts = sbuf[:n_acts]
         local_rot, transforms, node_rot, d_nodes, global_trans = _pose_block(sbuf[o_small:], J)
+        table = sbuf[o_table:] if n_table else None
         o_rot = (3 * N + 63) & ~63
         dbuf = torch.empty(o_rot + 4 * N, **f32)
         d_xyz, d_rot = dbuf[:3 * N].view(N, 3), dbuf[o_rot:].view(N, 4)
@@ -448,9 +465,9 @@ class _PoseDeform(torch.autograd.Function):
         L.check(lib.riggs_lbs_forward_fk(N, J, K, x.data_ptr(), joints.data_ptr(), parents_i32.data_ptr(), rho.data_ptr(),
                                          local_rot.data_ptr(), global_trans.data_ptr(), L.ptr(mflat), L.ptr(weight_mod),
                                          transforms.data_ptr(), node_rot.data_ptr(), d_nodes.data_ptr(), d_xyz.data_ptr(),
-                                         d_rot.data_ptr(), L.ptr(_bone_table(N, x.device)), st), "riggs_lbs_forward_fk")
+                                         d_rot.data_ptr(), L.ptr(table), st), "riggs_lbs_forward_fk")
         ctx.save_for_backward(acts, local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod,
-                              *params)
+                              table, *params)
         ctx.cfg = (depth, width, multires, skip, n_rot, K)
         ctx.sync = sync
         ctx.mask_shape = None if mask is None else mask.shape
@@ -459,13 +476,15 @@ class _PoseDeform(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_rot, g_nodes, g_local_rot, g_global_trans, g_transforms, _g_node_rot):
-        acts, local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod, *params = ctx.saved_tensors
+        (acts, local_rot, global_trans, rho, mflat, x, joints, parents_i32, transforms, node_rot, weight_mod, table,
+         *params) = ctx.saved_tensors
         depth, width, multires, skip, n_rot, K = ctx.cfg
         lib, J = L.lib(), joints.shape[0]
         f32 = dict(dtype=torch.float32, device=x.device)
         dG, dq, dgt, dgt_total = _pose_grad_block(torch.empty(_pose_grad_block_floats(J), **f32), J)  # (one allocation)
         dG, drho, dmask, dmod = _skinning_backward(K, x, joints, parents_i32, rho, transforms, node_rot, global_trans, mflat,
-                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[4])
+                                                   weight_mod, g_xyz, g_rot, g_transforms, dG, dgt, ctx.needs_input_grad[4],
+                                                   bone_table=table)
         if g_global_trans is not None:
             dgt = dgt + g_global_trans.reshape(-1)
         gn = None if g_nodes is None else g_nodes.contiguous()
@@ -794,7 +813,7 @@ class SkeletonWarp(NodeGaussians, nn.Module):
                 fx = getattr(self, "template_fixed", None)
                 d_xyz, d_rot, d_nodes, local_rot, global_trans, transforms, node_rot = torch.ops.riggs.pose_deform(
                     _time.reshape(1), self._rot_bias, sync, self._node_radius, mask, x, joints, par, weight_mod,
-                    fx[0] if fx else None, fx[1] if fx else None, _bone_table(x.shape[0], x.device), self.K, len(pn.net),
+                    fx[0] if fx else None, fx[1] if fx else None, _bone_table(joints.shape[0], x.device), self.K, len(pn.net),
                     pn.net[0].out_features, pn.multires, pn.skips[0], params)
             else:
                 d_xyz, d_rot, d_nodes, local_rot, global_trans, transforms, node_rot = _PoseDeform.apply(
