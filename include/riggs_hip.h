@@ -27,7 +27,7 @@ typedef void* riggs_stream; /* hipStream_t */
  * name; nor does a REMOVED symbol or option name: a consumer that still names it fails at symbol resolution, or with "unknown
  * option").  riggs_version() returns the value the library was built with; a consumer compiled against this header compares that
  * with its own RIGGS_ABI_VERSION and refuses the library when they differ (riggs_amd/_lib.py, csrc_torch/riggs_torch.cpp). */
-#define RIGGS_ABI_VERSION 101
+#define RIGGS_ABI_VERSION 102
 int riggs_version(void);
 const char* riggs_last_error(void);
 
@@ -944,28 +944,26 @@ int riggs_mlp_backward(int32_t N, int32_t out_ch, int32_t depth, int32_t skip, c
  * aligned.
  * sigmoid_out (N, out_ch; may be NULL): the head's output went through riggs_mlp_epilogue.sigmoid — the cotangent of the head is
  * g_out * s (1 - s), which is what is tested for a non-zero and gathered into g_live (no sigmoid_backward launch in front).
- * scale (device float; may be NULL): receives the fp16 gradient scale of riggs_mlp_grad_scale over that cotangent — per-block
+ * scale (device float; may be NULL): receives the fp16 gradient scale of riggs_mlp_cotangent over that cotangent — per-block
  * maxima from the first launch, reduced by the second: no launch and no atomic of its own. */
 size_t riggs_mlp_live_rows_workspace_bytes(int32_t N);
 int riggs_mlp_live_rows(int32_t N, int32_t out_ch, int32_t in_ch, const float* g_out, const float* sigmoid_out, const void* x_emb_bf16,
                         void* workspace, int32_t* live_idx, int32_t* live_count, void* x_live_bf16, float* g_live, float* scale,
                         riggs_stream stream);
-/* The g_scale of the fp16 format from the gradient itself: scale[0] = 2^floor(log2(1024 / max|g|)) (max|g| clamped at 1e-30), two
- * launches, no host synchronisation.  zero_word: a device u32 that is ZERO on entry (the caller clears it once) and zero again
- * behind the call. */
-int riggs_mlp_grad_scale(int64_t n, const float* g, float* scale, uint32_t* zero_word, riggs_stream stream);
-/* riggs_mlp_grad_scale with an L2 regulariser on the MLP's OUTPUT folded in — the template offsets' term of the stage-2
- * objective, train_rig.py:446-454: lambda * mean(template_offsets^2) over all Gaussians (x1e3 on the template frame) —
- *   g_eff = g + coef[0] * out   (n floats each; coef: a device scalar = 2 lambda / n, refreshed by the host between replays),
- * scale[0] as riggs_mlp_grad_scale from max|g_eff|, mean_sq[0] (may be NULL) = mean(out^2), the value the reference logs.
- * The same two launches; partials512: 512 floats of scratch.  The data-gradient and weight-gradient passes then read g_eff. */
-int riggs_mlp_l2_grad_scale(int64_t n, const float* g, const float* out, const float* coef, float* g_eff, float* scale,
-                            uint32_t* zero_word, float* partials512, float* mean_sq, riggs_stream stream);
-/* The general form (the same two launches): the cotangent the data-gradient pass reads, for an (N, out_ch) head,
+/* The cotangent the data-gradient pass reads, for an (N, out_ch) head, and the g_scale of the fp16 format taken from it — two
+ * launches, no host synchronisation:
  *   g_eff = (g + g_rows * row_mask[row]) * [s (1 - s)] + l2_coef[0] * l2_out
+ *   scale[0] = 2^floor(log2(1024 / max|g_eff|))   (max|g_eff| clamped at 1e-30)
  * g, g_rows (N, out_ch): at least one; row_mask (N; NULL = 1; needs g_rows): the motion mask that multiplied the head's output on
  * its way into res_out (riggs_mlp_epilogue); sigmoid_out (N, out_ch; NULL = no factor): the head's sigmoid-ed output;
- * l2_out / l2_coef (both or neither): the L2 term above.  scale / zero_word / partials512 / mean_sq as above. */
+ * l2_out / l2_coef (both or neither): an L2 regulariser on the MLP's OUTPUT — the template offsets' term of the stage-2
+ * objective, train_rig.py:446-454: lambda * mean(template_offsets^2) over all Gaussians (x1e3 on the template frame); l2_out is
+ * that output, l2_coef a device scalar = 2 lambda / (N out_ch), refreshed by the host between replays; mean_sq[0] (may be NULL)
+ * then receives mean(l2_out^2), the value the reference logs.
+ * g_eff may be NULL exactly when the cotangent is g itself (g given; g_rows, sigmoid_out and l2_out NULL): g is read for its
+ * maximum and nothing but scale is written.  Anything else with g_eff == NULL is refused.
+ * zero_word: a device u32 that is ZERO on entry (the caller clears it once) and zero again behind the call; partials512: 512
+ * floats of scratch.  g, l2_out and g_eff 16-byte aligned; N * out_ch < 2^31 (a flat tensor of n floats: N = n, out_ch = 1). */
 int riggs_mlp_cotangent(int32_t N, int32_t out_ch, const float* g, const float* g_rows, const float* row_mask,
                         const float* sigmoid_out, const float* l2_out, const float* l2_coef, float* g_eff, float* scale,
                         uint32_t* zero_word, float* partials512, float* mean_sq, riggs_stream stream);
@@ -977,34 +975,26 @@ int32_t riggs_mlp_rows_per_workgroup(void);
  *   dW_out = (g_out · g_scale)^T · acts_{depth-1},   db_l = sum_n dpre_l,   db_out = sum_n g_out · g_scale
  * streamed once by one workgroup per CU (split over the Gaussians, fp32 accumulators, LDS-direct loads — mlp_wgrad.hip), the
  * split partials summed, divided by g_scale (NULL = 1) and written to the fp32 tensors torch.autograd hands back:
- * grad_weights[l] (256, K_true) row-major with K_true = in_ch / in_ch + 256 (layer skip + 1) / 256, grad_biases[l] (256),
- * grad_w_out (out_ch, 256), grad_b_out (out_ch).  x_emb_bf16 / acts_bf16 / dpre_bf16: the buffers of riggs_mlp_forward /
- * riggs_mlp_backward, same format.  workspace: riggs_mlp_wgrad_workspace_bytes bytes, 256-byte aligned, contents irrelevant
- * (depends on N, the shape and the device's CU count). */
+ * grad_weights[l] (256, K_true) row-major with K_true = in_true / in_true + 256 (layer skip + 1) / 256, in_true = in_ch + tail_ch,
+ * grad_biases[l] (256), grad_w_out (out_ch, 256), grad_b_out (out_ch).  x_emb_bf16 / acts_bf16 / dpre_bf16: the buffers of
+ * riggs_mlp_forward / riggs_mlp_backward, same format.  workspace: riggs_mlp_wgrad_workspace_bytes bytes, 256-byte aligned,
+ * contents irrelevant (depends on N, the shape and the device's CU count).
+ * tail_ch / tail: an MLP whose input ends in tail_ch values that are THE SAME FOR EVERY ROW (DeformMLP: the pose vector,
+ * skeleton_warp.py:152 `pose = local_rot.detach().reshape(-1)[None].expand(N, -1)`): the masters' weights of the two layers that
+ * read the input have in_ch + tail_ch input columns, the packed operands and x_emb_bf16 only the first in_ch (riggs_mlp_pack with
+ * the same tail_ch); the gradient of the tail's columns is (bias gradient) x tail — written by the launch that sums the
+ * partials.  tail: tail_ch floats on the device.  tail_ch = 0 with tail = NULL: the plain MLP. */
 size_t riggs_mlp_wgrad_workspace_bytes(int32_t N, int32_t in_ch, int32_t depth, int32_t skip);
-int riggs_mlp_wgrad(int32_t N, int32_t in_ch, int32_t out_ch, int32_t depth, int32_t skip, const void* x_emb_bf16,
-                    const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale, void* workspace,
-                    size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases, float* grad_w_out,
-                    float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream);
-/* riggs_mlp_wgrad for an MLP whose input ends in tail_ch values that are THE SAME FOR EVERY ROW (DeformMLP: the pose vector,
- * /root/reference/skeleton_utils/skeleton_warp.py:152 `pose = local_rot.detach().reshape(-1)[None].expand(N, -1)`): the masters'
- * weights of the two layers that read the input have in_ch + tail_ch input columns, the packed operands and x_emb_bf16 only the
- * first in_ch (riggs_mlp_pack_tail); the gradient of the tail's columns is (bias gradient) x tail — written by the launch that
- * sums the partials.  tail: tail_ch floats on the device.  tail_ch = 0: riggs_mlp_wgrad. */
-int riggs_mlp_wgrad_tail(int32_t N, int32_t in_ch, int32_t tail_ch, const float* tail, int32_t out_ch, int32_t depth, int32_t skip,
-                         const void* x_emb_bf16, const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale,
-                         void* workspace, size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases,
-                         float* grad_w_out, float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream);
+int riggs_mlp_wgrad(int32_t N, int32_t in_ch, int32_t tail_ch, const float* tail, int32_t out_ch, int32_t depth, int32_t skip,
+                    const void* x_emb_bf16, const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale,
+                    void* workspace, size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases,
+                    float* grad_w_out, float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream);
 /* fp32 master weights ((256, K_true) row-major per layer, (out_ch, 256) for the head) -> every bf16 operand the two kernels
- * read (layouts above), in one launch. */
-int riggs_mlp_pack(int32_t in_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights, const float* w_out,
-                   void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16, void* w_out_t_bf16,
-                   int32_t fp16, riggs_stream stream);
-/* riggs_mlp_pack for masters with a constant input tail (riggs_mlp_wgrad_tail): K_true = in_ch + tail_ch (+ 256 in layer skip + 1);
+ * read (layouts above), in one launch.  tail_ch > 0 (riggs_mlp_wgrad): K_true = in_ch + tail_ch (+ 256 in layer skip + 1), and
  * the tail's columns are left out of the packed operands. */
-int riggs_mlp_pack_tail(int32_t in_ch, int32_t tail_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights,
-                        const float* w_out, void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16,
-                        void* w_out_t_bf16, int32_t fp16, riggs_stream stream);
+int riggs_mlp_pack(int32_t in_ch, int32_t tail_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights,
+                   const float* w_out, void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16,
+                   void* w_out_t_bf16, int32_t fp16, riggs_stream stream);
 /* ... and what they contribute: bias_eff (2, 256) = [b_first + W_first[:, in_ch : in_ch + tail_ch] tail,
  * b_skip + W_skip[:, in_ch : in_ch + tail_ch] tail] in fp32 — the biases riggs_mlp_forward takes for layer 0 and layer skip + 1
  * (network_utils.py:46-51: h = cat([x_emb, t_emb]) enters both).  One launch per forward: the tail changes with every frame. */

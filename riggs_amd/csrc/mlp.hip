@@ -657,7 +657,7 @@ __global__ __launch_bounds__(256) void mlp_live_flags_kernel(int N, int out_ch, 
 }
 // Launch 2: block b sums the counts in front of it (<= a few thousand words), ranks its live rows and copies them; with `scale`
 // every block also takes the maximum over ALL blocks' maxima (the same few thousand words) — block 0 turns it into the fp16
-// gradient scale of riggs_mlp_grad_scale, which then costs no launch of its own (and no atomic).
+// gradient scale of riggs_mlp_cotangent, which then costs no launch of its own (and no atomic).
 __global__ __launch_bounds__(256) void mlp_live_gather_kernel(int N, int out_ch, int in_pad, const float* __restrict__ g_out,
                                                               const float* __restrict__ sig,
                                                               const unsigned short* __restrict__ xb,
@@ -723,7 +723,7 @@ __global__ __launch_bounds__(256) void mlp_live_gather_kernel(int N, int out_ch,
 // and ~60 small conversion / padding / transposition launches per MLP were a tenth of a heads-on training iteration)
 struct MlpPackDesc {
   int in_ch, in_pad, out_ch, depth, skip;
-  int tail_ch;                   // columns of the masters' input part that are NOT packed (riggs_mlp_pack_tail): they multiply a
+  int tail_ch;                   // columns of the masters' input part that are NOT packed (riggs_mlp_pack: tail_ch): they multiply a
                                  // vector that is the same for every row and enter the layer through its bias (riggs_mlp_tail_bias)
   const float* W[10];            // (256, K_true): K_true = in_ch + tail_ch, in_ch + tail_ch + 256 (layer skip + 1) or 256
   const float* Wout;             // (out_ch, 256)
@@ -943,9 +943,9 @@ int riggs_mlp_embed(int32_t N, int32_t multires, int32_t n_tail, const float* x,
   return 0;
 }
 
-int riggs_mlp_pack_tail(int32_t in_ch, int32_t tail_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights,
-                        const float* w_out, void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16,
-                        void* w_out_t_bf16, int32_t fp16, riggs_stream stream) {
+int riggs_mlp_pack(int32_t in_ch, int32_t tail_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights,
+                   const float* w_out, void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16,
+                   void* w_out_t_bf16, int32_t fp16, riggs_stream stream) {
   RIGGS_REQUIRE(depth >= 1 && depth <= 10 && in_ch >= 1 && in_ch <= MLP_MAX_IN && out_ch >= 1 && out_ch <= 32 && skip >= 0 &&
                 skip < depth - 1 && tail_ch >= 0 && tail_ch <= 4096, "MLP shape out of range");
   MlpPackDesc d;
@@ -960,13 +960,6 @@ int riggs_mlp_pack_tail(int32_t in_ch, int32_t tail_ch, int32_t out_ch, int32_t 
   else hipLaunchKernelGGL(mlp_pack_kernel<false>, dim3(32, depth + 1), dim3(256), 0, (hipStream_t)stream, d);
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
-}
-
-int riggs_mlp_pack(int32_t in_ch, int32_t out_ch, int32_t depth, int32_t skip, const float* const* weights, const float* w_out,
-                   void* const* weights_bf16, void* const* weights_t_bf16, void* w_out_bf16, void* w_out_t_bf16,
-                   int32_t fp16, riggs_stream stream) {
-  return riggs_mlp_pack_tail(in_ch, 0, out_ch, depth, skip, weights, w_out, weights_bf16, weights_t_bf16, w_out_bf16, w_out_t_bf16, fp16,
-                             stream);
 }
 
 int riggs_mlp_tail_bias(int32_t in_ch, int32_t tail_ch, const float* w_first, const float* b_first, const float* w_skip,

@@ -263,45 +263,17 @@ __global__ __launch_bounds__(256) void mlp_gob_kernel(int N, int rows, int out_c
   *reinterpret_cast<wg_h8*>(gob + e * 8) = v;
 }
 
-// max |g| over a tensor -> the power of two that lifts it to ~2^10 (riggs_mlp_grad_scale): the maximum is taken on the bit
-// patterns (non-negative floats order like unsigned integers) into a word that is zero between calls; a second, one-thread launch
-// turns it into the scale and clears the word again
-__global__ __launch_bounds__(256) void mlp_amax_kernel(int64_t n, const float* __restrict__ g, uint32_t* __restrict__ word) {
-  uint32_t m = 0u;
-  const int64_t n4 = n >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const uint4 v = reinterpret_cast<const uint4*>(g)[i];
-    m = max(max(m, v.x & 0x7FFFFFFFu), max(max(v.y & 0x7FFFFFFFu, v.z & 0x7FFFFFFFu), v.w & 0x7FFFFFFFu));
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) m = max(m, __float_as_uint(g[(n4 << 2) + threadIdx.x]) & 0x7FFFFFFFu);
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  // ONE atomic per workgroup, a few hundred workgroups: atomics on one address are served one after the other at the memory
-  // side (one per wave of 2 048 workgroups were 8 192 of them: 70 us for a 6 us read)
-  __shared__ uint32_t s_m[4];
-  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
-    if (m) atomicMax(word, m);
-  }
-}
-__global__ void mlp_scale_kernel(uint32_t* __restrict__ word, float* __restrict__ scale) {
-  const float amax = fmaxf(__uint_as_float(word[0]), 1e-30f);
-  scale[0] = exp2f(floorf(log2f(1024.0f / amax)));
-  word[0] = 0u;
-}
-
-
-// The DeformMLP's L2 regulariser folded into its backward (train_rig.py:446-454: lambda * mean(template_offsets^2) over ALL
-// Gaussians, x1e3 on the template frame): the cotangent the data-gradient pass reads becomes  g_eff = g + coef * out  with
-// coef = 2 lambda / (3 N) a device scalar — written by the launch that takes max|g| for the fp16 gradient scale anyway, so the
-// term costs no launch of its own — and the launch that turns the maximum into the scale also finishes  mean(out^2)  (the value
-// the reference logs) from the per-workgroup partial sums, in a fixed order.
-// (generalised in round 6 — riggs_mlp_cotangent: the cotangent may also be the SUM of a direct term and a per-row-masked one,
-//   g_eff = (g + g_rows * row_mask[row]) * [s (1 - s)] + coef * out ,
-// every piece optional: g_rows * row_mask is what reaches the template offsets through  d_xyz = blend + offsets * motion_mask
-// (skeleton_warp.py:152-161; was a torch mul in front), s (1 - s) the sigmoid folded into the WeightMLP's head (was a
-// sigmoid_backward launch).)
+// The cotangent the data-gradient pass reads and its fp16 gradient scale, in two launches (riggs_mlp_cotangent):
+//   g_eff = (g + g_rows * row_mask[row]) * [s (1 - s)] + coef * out ,   scale = 2^floor(log2(1024 / max|g_eff|)) ,
+// every piece optional.  g_rows * row_mask is what reaches the template offsets through  d_xyz = blend + offsets * motion_mask
+// (skeleton_warp.py:152-161); s (1 - s) the sigmoid folded into the WeightMLP's head; coef * out the DeformMLP's L2 regulariser
+// (train_rig.py:446-454: lambda * mean(template_offsets^2) over ALL Gaussians, x1e3 on the template frame; coef = 2 lambda / (3 N)
+// a device scalar), whose value mean(out^2) — what the reference logs — the second launch finishes from per-workgroup partial
+// sums, in a fixed order.  The maximum is taken on the bit patterns (non-negative floats order like unsigned integers) into a
+// word that is zero between calls; the second launch turns it into the scale and clears the word again.
+// g_eff == nullptr: the cotangent is g itself — read for its maximum in whole 16-byte loads, nothing stored (a template
+// parameter of the one kernel: as a run-time branch the call measured just outside the spread of the two-argument kernel it
+// replaced — NOTES.md, profiles/mlp_one_cotangent_times.json).
 struct MlpCot {
   int64_t n;
   int out_ch;
@@ -315,36 +287,50 @@ __device__ __forceinline__ float mlp_cot_value(const MlpCot& c, int64_t i, float
   if (c.out) v += coef * c.out[i];
   return v;
 }
-__global__ __launch_bounds__(256) void mlp_l2_amax_kernel(MlpCot c, uint32_t* __restrict__ word, float* __restrict__ partials) {
-  const float coef = c.coef ? c.coef[0] : 0.f;
+template <bool G_ONLY>  // G_ONLY: c.g_eff == nullptr
+__global__ __launch_bounds__(256) void mlp_cotangent_kernel(MlpCot c, uint32_t* __restrict__ word, float* __restrict__ partials) {
   uint32_t m = 0u;
   float ss = 0.f;
   const int64_t n4 = c.n >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    float4 e;
-    if (!c.g_rows && !c.sig && c.g && c.out) {  // the plain L2 form: whole vectors
-      const float4 gv = reinterpret_cast<const float4*>(c.g)[i], ov = reinterpret_cast<const float4*>(c.out)[i];
-      e.x = gv.x + coef * ov.x; e.y = gv.y + coef * ov.y; e.z = gv.z + coef * ov.z; e.w = gv.w + coef * ov.w;
-    } else {
-      e.x = mlp_cot_value(c, 4 * i, coef); e.y = mlp_cot_value(c, 4 * i + 1, coef);
-      e.z = mlp_cot_value(c, 4 * i + 2, coef); e.w = mlp_cot_value(c, 4 * i + 3, coef);
+  if constexpr (G_ONLY) {  // g alone, nowhere to write it
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+      const uint4 v = reinterpret_cast<const uint4*>(c.g)[i];
+      m = max(max(m, v.x & 0x7FFFFFFFu), max(max(v.y & 0x7FFFFFFFu, v.z & 0x7FFFFFFFu), v.w & 0x7FFFFFFFu));
     }
-    reinterpret_cast<float4*>(c.g_eff)[i] = e;
-    m = max(max(m, __float_as_uint(e.x) & 0x7FFFFFFFu), max(max(__float_as_uint(e.y) & 0x7FFFFFFFu, __float_as_uint(e.z) & 0x7FFFFFFFu),
-                                                             __float_as_uint(e.w) & 0x7FFFFFFFu));
-    if (c.out) {
-      const float4 ov = reinterpret_cast<const float4*>(c.out)[i];
-      ss += (ov.x * ov.x + ov.y * ov.y) + (ov.z * ov.z + ov.w * ov.w);
+    if (blockIdx.x == 0 && threadIdx.x < (int)(c.n & 3)) m = max(m, __float_as_uint(c.g[(n4 << 2) + threadIdx.x]) & 0x7FFFFFFFu);
+  } else {
+    const float coef = c.coef ? c.coef[0] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+      float4 e;
+      if (!c.g_rows && !c.sig && c.g && c.out) {  // the plain L2 form: whole vectors
+        const float4 gv = reinterpret_cast<const float4*>(c.g)[i], ov = reinterpret_cast<const float4*>(c.out)[i];
+        e.x = gv.x + coef * ov.x; e.y = gv.y + coef * ov.y; e.z = gv.z + coef * ov.z; e.w = gv.w + coef * ov.w;
+      } else {
+        e.x = mlp_cot_value(c, 4 * i, coef); e.y = mlp_cot_value(c, 4 * i + 1, coef);
+        e.z = mlp_cot_value(c, 4 * i + 2, coef); e.w = mlp_cot_value(c, 4 * i + 3, coef);
+      }
+      reinterpret_cast<float4*>(c.g_eff)[i] = e;
+      m = max(max(m, __float_as_uint(e.x) & 0x7FFFFFFFu), max(max(__float_as_uint(e.y) & 0x7FFFFFFFu, __float_as_uint(e.z) & 0x7FFFFFFFu),
+                                                               __float_as_uint(e.w) & 0x7FFFFFFFu));
+      if (c.out) {
+        const float4 ov = reinterpret_cast<const float4*>(c.out)[i];
+        ss += (ov.x * ov.x + ov.y * ov.y) + (ov.z * ov.z + ov.w * ov.w);
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(c.n & 3)) {
+      const int64_t i = (n4 << 2) + threadIdx.x;
+      const float e = mlp_cot_value(c, i, coef);
+      c.g_eff[i] = e;
+      m = max(m, __float_as_uint(e) & 0x7FFFFFFFu);
+      if (c.out) ss += c.out[i] * c.out[i];
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(c.n & 3)) {
-    const int64_t i = (n4 << 2) + threadIdx.x;
-    const float e = mlp_cot_value(c, i, coef);
-    c.g_eff[i] = e;
-    m = max(m, __float_as_uint(e) & 0x7FFFFFFFu);
-    if (c.out) ss += c.out[i] * c.out[i];
+  for (int o = 32; o > 0; o >>= 1) {
+    m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    if constexpr (!G_ONLY) ss += __shfl_xor(ss, o);
   }
-  for (int o = 32; o > 0; o >>= 1) { m = max(m, (uint32_t)__shfl_xor((int)m, o)); ss += __shfl_xor(ss, o); }
+  // ONE atomic per workgroup, a few hundred workgroups: atomics on one address are served one after the other at the memory
+  // side (one per wave of 2 048 workgroups were 8 192 of them: 70 us for a 6 us read)
   __shared__ uint32_t s_m[4];
   __shared__ float s_s[4];
   if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = ss; }
@@ -352,12 +338,15 @@ __global__ __launch_bounds__(256) void mlp_l2_amax_kernel(MlpCot c, uint32_t* __
   if (threadIdx.x == 0) {
     m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
     if (m) atomicMax(word, m);
-    partials[blockIdx.x] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
+    if constexpr (!G_ONLY) {
+      if (c.out) partials[blockIdx.x] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
+    }
   }
 }
-__global__ __launch_bounds__(64) void mlp_l2_scale_kernel(uint32_t* __restrict__ word, float* __restrict__ scale,
-                                                          const float* __restrict__ partials, int n_partials, float inv_count,
-                                                          float* __restrict__ mean_sq) {
+// n_partials = 0 without the L2 term: there is no mean to finish
+__global__ __launch_bounds__(64) void mlp_cotangent_scale_kernel(uint32_t* __restrict__ word, float* __restrict__ scale,
+                                                                 const float* __restrict__ partials, int n_partials, float inv_count,
+                                                                 float* __restrict__ mean_sq) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n_partials; i += 64) s += partials[i];
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -379,7 +368,7 @@ struct WgBias {
   float* dst;         // (count)
   int splits, M, count, pad;
 };
-// the masters' columns of a constant input tail (riggs_mlp_wgrad_tail): dW[n][col_off + k] = db[n] * tail[k] — the row sums the
+// the masters' columns of a constant input tail (riggs_mlp_wgrad: tail_ch): dW[n][col_off + k] = db[n] * tail[k] — the row sums the
 // product's workgroups left beside their partials, times the tail
 struct WgRank1 {
   const float* part;  // (splits, M): the column sums of the layer's gradient operand
@@ -506,27 +495,14 @@ using namespace riggs;
 
 extern "C" {
 
-int riggs_mlp_grad_scale(int64_t n, const float* g, float* scale, uint32_t* zero_word, riggs_stream stream) {
-  RIGGS_REQUIRE(n >= 0 && scale && zero_word && (n == 0 || g), "riggs_mlp_grad_scale: bad arguments");
-  RIGGS_REQUIRE(((uintptr_t)g & 15) == 0, "riggs_mlp_grad_scale: the tensor must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  if (n > 0) {
-    const int64_t want = ((n >> 2) + 255) / 256;
-    hipLaunchKernelGGL(mlp_amax_kernel, dim3((unsigned)(want < 512 ? (want > 0 ? want : 1) : 512)), dim3(256), 0, s, n, g, zero_word);
-    RIGGS_HIP_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(mlp_scale_kernel, dim3(1), dim3(1), 0, s, zero_word, scale);
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-
 int riggs_mlp_cotangent(int32_t N, int32_t out_ch, const float* g, const float* g_rows, const float* row_mask, const float* sigmoid_out,
                         const float* l2_out, const float* l2_coef, float* g_eff, float* scale, uint32_t* zero_word, float* partials512,
                         float* mean_sq, riggs_stream stream) {
   RIGGS_REQUIRE(N >= 0 && out_ch >= 1 && out_ch <= 32 && scale && zero_word && partials512, "riggs_mlp_cotangent: bad arguments");
   RIGGS_REQUIRE((int64_t)N * out_ch < (1ll << 31), "riggs_mlp_cotangent: N x out_ch must be < 2^31");
-  RIGGS_REQUIRE(N == 0 || ((g || g_rows) && g_eff), "riggs_mlp_cotangent: tensors");
+  RIGGS_REQUIRE(g_eff || (g && !g_rows && !sigmoid_out && !l2_out),
+                "riggs_mlp_cotangent: g_eff may be NULL only when the cotangent is g itself (no g_rows, sigmoid_out or l2_out)");
+  RIGGS_REQUIRE(N == 0 || g || g_rows, "riggs_mlp_cotangent: tensors");
   RIGGS_REQUIRE((l2_out == nullptr) == (l2_coef == nullptr), "riggs_mlp_cotangent: l2_out and l2_coef come together");
   RIGGS_REQUIRE(row_mask == nullptr || g_rows != nullptr, "riggs_mlp_cotangent: row_mask without g_rows");
   RIGGS_REQUIRE((((uintptr_t)g | (uintptr_t)l2_out | (uintptr_t)g_eff) & 15) == 0, "riggs_mlp_cotangent: g, l2_out and g_eff must be 16-byte aligned");
@@ -539,31 +515,12 @@ int riggs_mlp_cotangent(int32_t N, int32_t out_ch, const float* g, const float* 
     MlpCot c;
     c.n = n; c.out_ch = out_ch; c.g = g; c.g_rows = g_rows; c.row_mask = row_mask; c.sig = sigmoid_out; c.out = l2_out; c.coef = l2_coef;
     c.g_eff = g_eff;
-    hipLaunchKernelGGL(mlp_l2_amax_kernel, dim3(blocks), dim3(256), 0, s, c, zero_word, partials512);
+    if (g_eff) hipLaunchKernelGGL(mlp_cotangent_kernel<false>, dim3(blocks), dim3(256), 0, s, c, zero_word, partials512);
+    else hipLaunchKernelGGL(mlp_cotangent_kernel<true>, dim3(blocks), dim3(256), 0, s, c, zero_word, partials512);
     RIGGS_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(mlp_l2_scale_kernel, dim3(1), dim3(64), 0, s, zero_word, scale, partials512, blocks, n > 0 ? 1.0f / (float)n : 0.f,
-                     l2_out ? mean_sq : nullptr);
-  RIGGS_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int riggs_mlp_l2_grad_scale(int64_t n, const float* g, const float* out, const float* coef, float* g_eff, float* scale,
-                            uint32_t* zero_word, float* partials512, float* mean_sq, riggs_stream stream) {
-  RIGGS_REQUIRE(n >= 0 && scale && zero_word && partials512 && coef, "riggs_mlp_l2_grad_scale: bad arguments");
-  RIGGS_REQUIRE(n == 0 || (g && out && g_eff), "riggs_mlp_l2_grad_scale: tensors");
-  RIGGS_REQUIRE((((uintptr_t)g | (uintptr_t)out | (uintptr_t)g_eff) & 15) == 0, "riggs_mlp_l2_grad_scale: the tensors must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  int blocks = 0;
-  if (n > 0) {
-    const int64_t want = ((n >> 2) + 255) / 256;
-    blocks = (int)(want < 512 ? (want > 0 ? want : 1) : 512);
-    MlpCot c;
-    c.n = n; c.out_ch = 1; c.g = g; c.g_rows = nullptr; c.row_mask = nullptr; c.sig = nullptr; c.out = out; c.coef = coef; c.g_eff = g_eff;
-    hipLaunchKernelGGL(mlp_l2_amax_kernel, dim3(blocks), dim3(256), 0, s, c, zero_word, partials512);
-    RIGGS_HIP_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(mlp_l2_scale_kernel, dim3(1), dim3(64), 0, s, zero_word, scale, partials512, blocks, n > 0 ? 1.0f / (float)n : 0.f, mean_sq);
+  hipLaunchKernelGGL(mlp_cotangent_scale_kernel, dim3(1), dim3(64), 0, s, zero_word, scale, partials512, l2_out ? blocks : 0,
+                     n > 0 ? 1.0f / (float)n : 0.f, l2_out ? mean_sq : nullptr);
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -575,18 +532,10 @@ size_t riggs_mlp_wgrad_workspace_bytes(int32_t N, int32_t in_ch, int32_t depth, 
   return P.bytes;
 }
 
-int riggs_mlp_wgrad(int32_t N, int32_t in_ch, int32_t out_ch, int32_t depth, int32_t skip, const void* x_emb_bf16,
-                    const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale, void* workspace,
-                    size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases, float* grad_w_out,
-                    float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream) {
-  return riggs_mlp_wgrad_tail(N, in_ch, 0, nullptr, out_ch, depth, skip, x_emb_bf16, acts_bf16, dpre_bf16, g_out, g_scale, workspace,
-                              workspace_bytes, grad_weights, grad_biases, grad_w_out, grad_b_out, n_rows_dev, fp16, stream);
-}
-
-int riggs_mlp_wgrad_tail(int32_t N, int32_t in_ch, int32_t tail_ch, const float* tail, int32_t out_ch, int32_t depth, int32_t skip,
-                         const void* x_emb_bf16, const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale,
-                         void* workspace, size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases,
-                         float* grad_w_out, float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream) {
+int riggs_mlp_wgrad(int32_t N, int32_t in_ch, int32_t tail_ch, const float* tail, int32_t out_ch, int32_t depth, int32_t skip,
+                    const void* x_emb_bf16, const void* acts_bf16, const void* dpre_bf16, const float* g_out, const float* g_scale,
+                    void* workspace, size_t workspace_bytes, float* const* grad_weights, float* const* grad_biases,
+                    float* grad_w_out, float* grad_b_out, const int32_t* n_rows_dev, int32_t fp16, riggs_stream stream) {
   RIGGS_REQUIRE(N >= 0 && depth >= 2 && depth <= 10, "MLP depth out of range");
   RIGGS_REQUIRE(tail_ch >= 0 && tail_ch <= 4096 && (tail_ch == 0 || tail), "MLP weight gradients: the constant tail");
   const int in_true = in_ch + tail_ch;  // the masters' input columns

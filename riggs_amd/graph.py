@@ -355,7 +355,7 @@ class GraphedTrainStep(GraphedFrame):
     ``lambda * mean(template_offsets^2)`` over ALL Gaussians, x1e3 on the template camera (train_rig.py:446-456) — and
     ``lambda_template_fixed`` — ``lambda * mean((local_rotation - (1,0,0,0))^2)`` on the template camera only (:474-482).  Both
     enter as cotangents INSIDE launches the backward makes anyway (the fused DeformMLP's gradient-scale launch,
-    ``riggs_mlp_l2_grad_scale``; the PoseMLP's backward, ``riggs_pose_mlp_backward_fk``): their coefficients are device scalars
+    ``riggs_mlp_cotangent``; the PoseMLP's backward, ``riggs_pose_mlp_backward_fk``): their coefficients are device scalars
     that ``run(is_template=...)`` refreshes, their values land in ``out["template_offsets_loss"]`` /
     ``out["template_fixed_loss"]`` (unweighted means, what the reference logs).  With the fp32 (torch) heads the L2 is a second
     autograd root instead."""

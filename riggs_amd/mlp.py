@@ -8,6 +8,11 @@ parameter gradients within ~2 % of the fp32 mirror; the incoming gradient is sca
 that half precision's narrow range is never the limit, and the parameter gradients are scaled back) or ``"bf16"``
 (8 bits, fp32's range, 3-11 % on the gradients).  The reference computes these MLPs in fp32
 (skeleton_utils/network_utils.py:6-112), so the path is OPT-IN (``SkeletonWarp.use_fused_heads(True)``).
+
+One C entry per step: ``riggs_mlp_pack`` (weights -> operands), ``riggs_mlp_forward``, ``riggs_mlp_cotangent`` (what the backward
+reads — the incoming gradient with the sigmoid's factor, the residual join's masked term and the L2 regulariser folded in — and its
+fp16 scale: ``cotangent`` / ``grad_scale``), ``riggs_mlp_live_rows`` (row-sparse heads), ``riggs_mlp_backward``, ``riggs_mlp_wgrad``.
+A constant input tail (``tail_ch``: DeformMLP's pose) is an argument of the pack and the weight gradients, not an entry of its own.
 """
 from __future__ import annotations
 
@@ -17,7 +22,6 @@ import torch
 
 from . import _lib as L
 
-ROWS = 64
 FORMATS = {"fp16": torch.float16, "bf16": torch.bfloat16}
 DEFAULT_FORMAT = "fp16"
 
@@ -82,9 +86,9 @@ class Packed:
         ws = [L.require_cuda_f32("weight", lin.weight.detach()) for lin in self.linears]
         wo = L.require_cuda_f32("head weight", self.head.weight.detach())
         src = (C.c_void_p * self.depth)(*[t.data_ptr() for t in ws])
-        L.check(L.lib().riggs_mlp_pack_tail(self.in_ch, self.tail_ch, self.out_ch, self.depth, self.skip, src, wo.data_ptr(), self._wp,
-                                            self._wtp, self.w_out.data_ptr(), self.w_out_t_bf16.data_ptr(), self.fp16, L.stream_ptr()),
-                "riggs_mlp_pack_tail")
+        L.check(L.lib().riggs_mlp_pack(self.in_ch, self.tail_ch, self.out_ch, self.depth, self.skip, src, wo.data_ptr(), self._wp,
+                                       self._wtp, self.w_out.data_ptr(), self.w_out_t_bf16.data_ptr(), self.fp16, L.stream_ptr()),
+                "riggs_mlp_pack")
         self._w_masters = ws
         self.b = [L.require_cuda_f32("bias", lin.bias.detach()) for lin in self.linears]  # (views of the masters)
         self.b_out = L.require_cuda_f32("head bias", self.head.bias.detach())
@@ -166,7 +170,19 @@ def forward(p: Packed, x_emb: torch.Tensor, want_acts: bool, xb: torch.Tensor = 
     return out, (acts, masks) if want_acts else None
 
 
-_ZERO_WORD = {}
+_SCRATCH = {}
+
+
+def _scratch(device):
+    """``riggs_mlp_cotangent``'s zero_word and partials512 as pointers, one pair of tensors per (device, stream): two heads' backwards
+    on two streams must not share the accumulator word.  Allocated (and the word cleared) on first use; every call leaves the
+    word zero again.  ``_SCRATCH`` holds (word, partials, their addresses)."""
+    key = (device, L.stream_ptr())
+    sc = _SCRATCH.get(key)
+    if sc is None:
+        word, partials = torch.zeros(1, dtype=torch.int32, device=device), torch.empty(512, device=device)
+        sc = _SCRATCH[key] = (word, partials, word.data_ptr(), partials.data_ptr())
+    return sc[2], sc[3]
 
 
 def _aligned(t: torch.Tensor) -> torch.Tensor:
@@ -178,44 +194,23 @@ def _aligned(t: torch.Tensor) -> torch.Tensor:
 def grad_scale(g_out: torch.Tensor) -> torch.Tensor:
     """The power of two (a device scalar: no host synchronisation) that lifts max|g_out| to ~2^10: with fp16 operands the
     gradients of a per-pixel-averaged loss (1e-6 .. 1e-9) would otherwise sit in half precision's subnormals.  Two launches
-    (``riggs_mlp_grad_scale``; as torch ops it was seven and a copy of the tensor)."""
+    (``riggs_mlp_cotangent`` without a ``g_eff``: the tensor is read, not copied; as torch ops it was seven and a copy)."""
     if g_out.numel() == 0:
         return torch.ones(1, device=g_out.device)
     g = _aligned(L.require_cuda_f32("g_out", g_out))
-    key = (g.device, L.stream_ptr())  # (one accumulator word per stream: two heads' backwards on two streams must not share it)
-    word = _ZERO_WORD.get(key)
-    if word is None:
-        word = _ZERO_WORD[key] = torch.zeros(1, dtype=torch.int32, device=g.device)
+    word, partials = _scratch(g.device)
     scale = torch.empty(1, device=g.device)
-    L.check(L.lib().riggs_mlp_grad_scale(g.numel(), g.data_ptr(), scale.data_ptr(), word.data_ptr(), L.stream_ptr()), "riggs_mlp_grad_scale")
+    L.check(L.lib().riggs_mlp_cotangent(g.numel(), 1, g.data_ptr(), None, None, None, None, None, None, scale.data_ptr(), word, partials,
+                                        None, L.stream_ptr()), "riggs_mlp_cotangent")
     return scale
-
-
-_L2_SCRATCH = {}
-
-
-def l2_grad_scale(g_out: torch.Tensor, out: torch.Tensor, coef: torch.Tensor, mean_sq: torch.Tensor = None):
-    """``riggs_mlp_l2_grad_scale``: ``g_eff = g_out + coef * out`` (the L2 regulariser on the MLP's output folded into its
-    cotangent; ``coef`` a device scalar), the fp16 gradient scale of ``g_eff`` and — into ``mean_sq`` when given — mean(out^2).
-    The two launches ``grad_scale`` makes anyway.  Returns ``(g_eff, scale)``."""
-    g = _aligned(L.require_cuda_f32("g_out", g_out))
-    o = _aligned(L.require_cuda_f32("out", out, tuple(g.shape)))
-    key = (g.device, L.stream_ptr())
-    sc = _L2_SCRATCH.get(key)
-    if sc is None:
-        sc = _L2_SCRATCH[key] = (torch.zeros(1, dtype=torch.int32, device=g.device), torch.empty(512, device=g.device))
-    g_eff = torch.empty_like(g)
-    scale = torch.empty(1, device=g.device)
-    L.check(L.lib().riggs_mlp_l2_grad_scale(g.numel(), g.data_ptr(), o.data_ptr(), coef.data_ptr(), g_eff.data_ptr(), scale.data_ptr(),
-                                            sc[0].data_ptr(), sc[1].data_ptr(), L.ptr(mean_sq), L.stream_ptr()), "riggs_mlp_l2_grad_scale")
-    return g_eff, scale
 
 
 def cotangent(g: torch.Tensor, g_rows: torch.Tensor, row_mask: torch.Tensor, sigmoid_out: torch.Tensor, l2_out: torch.Tensor,
               l2_coef: torch.Tensor, mean_sq: torch.Tensor = None):
     """``riggs_mlp_cotangent``: ``g_eff = (g + g_rows * row_mask[row]) * [s (1 - s)] + l2_coef * l2_out`` for an (N, out_ch) head —
     every piece optional (``g`` or ``g_rows`` must be there) — and the fp16 gradient scale of ``g_eff``; the two launches
-    ``grad_scale`` makes anyway, whatever is folded in.  Returns ``(g_eff, scale)``."""
+    ``grad_scale`` makes anyway, whatever is folded in.  With ``l2_out`` (the L2 regulariser on the MLP's output; ``l2_coef`` a
+    device scalar) mean(l2_out^2) goes into ``mean_sq`` when given.  Returns ``(g_eff, scale)``."""
     ref = g if g is not None else g_rows
     N, out_ch = ref.shape
     tens = {}
@@ -223,15 +218,12 @@ def cotangent(g: torch.Tensor, g_rows: torch.Tensor, row_mask: torch.Tensor, sig
         tens[name] = None if t is None else _aligned(L.require_cuda_f32(name, t, (N, out_ch)))
     if row_mask is not None:
         row_mask = L.require_cuda_f32("row_mask", row_mask.reshape(-1), (N,))
-    key = (ref.device, L.stream_ptr())
-    sc = _L2_SCRATCH.get(key)
-    if sc is None:
-        sc = _L2_SCRATCH[key] = (torch.zeros(1, dtype=torch.int32, device=ref.device), torch.empty(512, device=ref.device))
+    word, partials = _scratch(ref.device)
     g_eff = torch.empty(N, out_ch, device=ref.device)
     scale = torch.empty(1, device=ref.device)
     L.check(L.lib().riggs_mlp_cotangent(N, out_ch, L.ptr(tens["g"]), L.ptr(tens["g_rows"]), L.ptr(row_mask), L.ptr(tens["sigmoid_out"]),
                                         L.ptr(tens["l2_out"]), L.ptr(l2_coef) if l2_out is not None else None, g_eff.data_ptr(),
-                                        scale.data_ptr(), sc[0].data_ptr(), sc[1].data_ptr(), L.ptr(mean_sq), L.stream_ptr()),
+                                        scale.data_ptr(), word, partials, L.ptr(mean_sq), L.stream_ptr()),
             "riggs_mlp_cotangent")
     return g_eff, scale
 
@@ -302,88 +294,14 @@ def param_grads(p: Packed, xb: torch.Tensor, acts: torch.Tensor, dpre: torch.Ten
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     gwp = (C.c_void_p * p.depth)(*[t.data_ptr() for t in gw])
     gbp = (C.c_void_p * p.depth)(*[gb[l].data_ptr() for l in range(p.depth)])
-    L.check(L.lib().riggs_mlp_wgrad_tail(N, p.in_ch, p.tail_ch, L.ptr(tail) if p.tail_ch else None, p.out_ch, p.depth, p.skip,
-                                         xb.data_ptr(), acts.data_ptr(), dpre.data_ptr(), g_out.data_ptr(), L.ptr(scale), ws.data_ptr(),
-                                         nbytes, gwp, gbp, gwo.data_ptr(), gbo.data_ptr(), L.ptr(n_dev), p.fp16, L.stream_ptr()),
-            "riggs_mlp_wgrad_tail")
+    L.check(L.lib().riggs_mlp_wgrad(N, p.in_ch, p.tail_ch, L.ptr(tail) if p.tail_ch else None, p.out_ch, p.depth, p.skip,
+                                    xb.data_ptr(), acts.data_ptr(), dpre.data_ptr(), g_out.data_ptr(), L.ptr(scale), ws.data_ptr(),
+                                    nbytes, gwp, gbp, gwo.data_ptr(), gbo.data_ptr(), L.ptr(n_dev), p.fp16, L.stream_ptr()),
+            "riggs_mlp_wgrad")
     out = []
     for l in range(p.depth):
         out += [gw[l], gb[l]]
     return out + [gwo, gbo]
-
-
-# ---- the same gradients through the library (torch.bmm = hipBLASLt): what ``param_grads`` replaced; kept as the comparison
-# the tests and tools/mlp_kernel_time.py run beside it, never called by the product path
-def _wgrad(d: torch.Tensor, a: torch.Tensor, splits: int = 128) -> torch.Tensor:
-    """d^T · a for d (N, M), a (N, K) in bf16 with fp32 output.  The reduction runs over N = 3e5 rows: one GEMM with
-    K_gemm = N leaves the library without parallelism (0.63 ms at 256 x 256 outputs); a batched GEMM over `splits` row
-    blocks plus a sum is 8x faster (0.08 ms)."""
-    N = d.shape[0]
-    n = N // splits
-    if n < 64:
-        return torch.mm(d.t(), a, out_dtype=torch.float32)
-    main = n * splits
-    out = torch.bmm(d[:main].view(splits, n, -1).transpose(1, 2), a[:main].view(splits, n, -1), out_dtype=torch.float32).sum(0)
-    if main < N:
-        out = out + torch.mm(d[main:].t(), a[main:], out_dtype=torch.float32)
-    return out
-
-
-def _wgrad_multi(d: torch.Tensor, a: torch.Tensor, splits: int = 128) -> torch.Tensor:
-    """``_wgrad`` for a stack of layers: d (L, N, M), a (L, N, K) -> (L, M, K), one batched GEMM over L x splits blocks.
-
-    The (layer, split) axes only merge into one batch axis without a copy when the split count divides N, so the
-    divisor of N nearest ``splits`` is used; without one in [splits/2, 2*splits] the layers go one at a time."""
-    Lr, N = d.shape[0], d.shape[1]
-    best = 0
-    for c in range(splits // 2, 2 * splits + 1):
-        if N % c == 0 and abs(c - splits) < abs(best - splits):
-            best = c
-    if best == 0 or N // best < 64:
-        return torch.stack([_wgrad(d[i], a[i], splits) for i in range(Lr)])
-    n = N // best
-    dm = d.view(Lr * best, n, d.shape[2])
-    am = a.view(Lr * best, n, a.shape[2])
-    return torch.bmm(dm.transpose(1, 2), am, out_dtype=torch.float32).view(Lr, best, d.shape[2], a.shape[2]).sum(1)
-
-
-_ONES = {}
-
-
-def _colsum(d: torch.Tensor) -> torch.Tensor:
-    """Column sums of a tall bf16 matrix in fp32, as a (split-K) GEMM with a block of ones: torch's column reduction of a
-    (3e5, 256) bf16 tensor takes 0.09 ms and of a (3e5, 23) fp32 one 0.6 ms; this is ~0.03 ms."""
-    key = (d.device, d.shape[0], d.dtype)
-    ones = _ONES.get(key)
-    if ones is None:
-        ones = _ONES[key] = torch.ones(d.shape[0], 8, dtype=d.dtype, device=d.device)
-    return _wgrad(d, ones)[:, 0].contiguous()
-
-
-def library_param_grads(p: Packed, xb: torch.Tensor, acts: torch.Tensor, dpre: torch.Tensor, db: torch.Tensor, g_out: torch.Tensor,
-                        scale: torch.Tensor = None):
-    """``param_grads`` through library GEMMs (comparison only; ``db`` from ``backward_data(..., bias_sums=True)``)."""
-    # every layer's product with the previous layer's activations has the same shape — the skip layer's hidden block
-    # included — so layers 1 .. depth - 1 are ONE batched split-K GEMM; the two products with the embedding stay single calls
-    if p.tail_ch:
-        raise ValueError("library_param_grads: the comparison path knows no constant tail")
-    gws = [None] * p.depth
-    ls = p.skip + 1
-    xb = xb[:g_out.shape[0]]
-    g_run = _wgrad_multi(dpre[1:p.depth], acts[0:p.depth - 1])
-    for l in range(1, p.depth):
-        gws[l] = g_run[l - 1]
-    gws[0] = _wgrad(dpre[0], xb)[:, :p.in_ch]
-    gws[ls] = torch.cat([_wgrad(dpre[ls], xb)[:, :p.in_ch], gws[ls]], 1)
-    grads = []
-    for l in range(p.depth):
-        grads += [gws[l], db[l]]
-    gob = torch.nn.functional.pad(g_out if scale is None else g_out * scale, (0, 32 - p.out_ch)).to(p.dtype)
-    grads += [_wgrad(gob, acts[p.depth - 1])[:p.out_ch], _colsum(gob)[:p.out_ch]]
-    if scale is not None:  # every product above carries the factor once: take it out again (a power of two: exact)
-        grads = [g.contiguous() for g in grads]
-        torch._foreach_mul_(grads, torch.reciprocal(scale).reshape(()))
-    return grads
 
 
 class _FusedMLP(torch.autograd.Function):
@@ -426,11 +344,21 @@ class _FusedMLP(torch.autograd.Function):
         g_res = None if g_res is None else g_res.contiguous()
         sig = ctx.out if ctx.sig else None
         plain = g_res is None and ctx.l2 is None  # the cotangent is g_out (x the sigmoid's factor)
-        if ctx.sparse and plain:
+        if ctx.sparse and plain:  # (the compaction's own two launches test g_out x the sigmoid's factor and take its scale)
             (xb,) = ctx.saved_tensors
             _, count, xl, gl, scale = live_rows(p, g_out, xb, sig, want_scale=True)
-            if not p.fp16:
-                scale = None
+        else:
+            if plain and sig is None:
+                scale = grad_scale(g_out) if p.fp16 else None
+            else:
+                l2o, l2c, msq = (ctx.out, ctx.l2[0], ctx.l2[1]) if ctx.l2 is not None else (None, None, None)
+                g_out, scale = cotangent(g_out, g_res, ctx.res_mask if g_res is not None else None, sig, l2o, l2c, msq)
+            if ctx.sparse:
+                (xb,) = ctx.saved_tensors
+                _, count, xl, gl = live_rows(p, g_out, xb)
+        if not p.fp16:
+            scale = None
+        if ctx.sparse:  # the forward again, on the live rows alone (their number stays on the device)
             if p.tail_ch:
                 p.set_tail(ctx.tail)  # (the repeated forward reads the biases of THIS call's frame)
             _, (acts, masks) = forward(p, xl[:ctx.n], True, xl, n_dev=count)
@@ -438,26 +366,9 @@ class _FusedMLP(torch.autograd.Function):
             grads = param_grads(p, xl, acts, dpre, gl, scale, n_dev=count, tail=ctx.tail)
             ctx.head.last_live_count = count
         else:
-            if plain and sig is None:
-                scale = grad_scale(g_out) if p.fp16 else None
-            else:
-                l2o, l2c, msq = (ctx.out, ctx.l2[0], ctx.l2[1]) if ctx.l2 is not None else (None, None, None)
-                g_out, scale = cotangent(g_out, g_res, ctx.res_mask if g_res is not None else None, sig, l2o, l2c, msq)
-                if not p.fp16:
-                    scale = None
-            if ctx.sparse:
-                (xb,) = ctx.saved_tensors
-                _, count, xl, gl = live_rows(p, g_out, xb)
-                if p.tail_ch:
-                    p.set_tail(ctx.tail)
-                _, (acts, masks) = forward(p, xl[:ctx.n], True, xl, n_dev=count)
-                dpre, _ = backward_data(p, gl, masks, scale, bias_sums=False, n_dev=count)
-                grads = param_grads(p, xl, acts, dpre, gl, scale, n_dev=count, tail=ctx.tail)
-                ctx.head.last_live_count = count
-            else:
-                xb, acts, masks = ctx.saved_tensors
-                dpre, _ = backward_data(p, g_out, masks, scale, bias_sums=False)
-                grads = param_grads(p, xb, acts, dpre, g_out, scale, tail=ctx.tail)
+            xb, acts, masks = ctx.saved_tensors
+            dpre, _ = backward_data(p, g_out, masks, scale, bias_sums=False)
+            grads = param_grads(p, xb, acts, dpre, g_out, scale, tail=ctx.tail)
         return (None, None, None, g_res if ctx.res else None, None) + tuple(grads)
 
 

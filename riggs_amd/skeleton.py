@@ -595,7 +595,7 @@ class SkeletonWarp(NodeGaussians, nn.Module):
         self.template_offsets = None
         # the stage-2 objective's two regularisers as cotangents inside this module's own backward launches (set per call by
         # riggs_amd.graph.GraphedTrainStep; None: a caller that writes the terms in torch — the reference's train_rig.py:446-482
-        # — gets them through autograd): (coef, mean_sq) device scalars for the fused DeformMLP (riggs_mlp_l2_grad_scale),
+        # — gets them through autograd): (coef, mean_sq) device scalars for the fused DeformMLP (riggs_mlp_cotangent),
         # (coef, loss) for the PoseMLP's backward (riggs_pose_mlp_backward_fk)
         self.template_l2 = None
         self.template_fixed = None

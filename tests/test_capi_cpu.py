@@ -279,6 +279,15 @@ def test_argument_validation_of_the_next_row_entries_needs_no_gpu():
         rc = L.riggs_skeleton_projection_forward(j, s, m, N, N, N, N, 1.0, 1.0, 0.0, 0.0, N, N, N, N, N, N)
         assert rc != 0 and L.riggs_last_error()
     assert L.riggs_skeleton_projection_state_floats(24, 41, 1500) == 2 * 41 * 23 + 2 * 1500 + 6 * 23
+    # fused MLP heads: the cotangent without a g_eff is g alone (dummy non-NULL pointers: refused before any launch) ...
+    P = 4096
+    for g_rows, sig, l2_out, l2_coef in ((P, N, N, N), (N, P, N, N), (N, N, P, P)):
+        rc = L.riggs_mlp_cotangent(8, 3, P, g_rows, N, sig, l2_out, l2_coef, N, P, P, P, N, N)
+        assert rc != 0 and b"g_eff" in L.riggs_last_error()
+    assert L.riggs_mlp_cotangent(8, 3, N, N, N, N, N, N, N, P, P, P, N, N) != 0 and b"g_eff" in L.riggs_last_error()  # (nor without g)
+    # ... and the weight gradients of a constant tail need the tail
+    rc = L.riggs_mlp_wgrad(8, 27, 96, N, 3, 8, 4, *([P] * 6), 1 << 20, *([P] * 4), N, 1, N)
+    assert rc != 0 and b"tail" in L.riggs_last_error()
 
 
 def test_integration_stub_matches_the_header_struct():

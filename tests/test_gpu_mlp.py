@@ -129,7 +129,7 @@ def test_param_grads_kernel_equals_the_products_of_its_operands(N, fmt):
         sc = M.grad_scale(g) if fmt == "fp16" else None
         dpre, db = M.backward_data(pk, g, masks, sc)
         got = M.param_grads(pk, xb, acts, dpre, g, sc)
-        lib = M.library_param_grads(pk, xb, acts, dpre, db, g, sc)
+        lib = R.library_param_grads(pk, xb, acts, dpre, db, g, sc)
         inv = 1.0 if sc is None else 1.0 / float(sc)
         gob = (g if sc is None else g * sc).to(pk.dtype).double()
         x64 = xb[:N, :pk.in_ch].double()
@@ -183,7 +183,7 @@ def test_stored_activations_are_the_layers_outputs(N, fmt):
 def test_constant_input_tail_through_the_biases(N, fmt):
     """DeformMLP's pose is ONE vector for all rows (skeleton_warp.py:152): with ``tail_ch`` the head packs the positional
     embedding alone, the pose enters through the two biases in fp32 (riggs_mlp_tail_bias) and its weight columns' gradient is
-    (bias gradient) x pose (riggs_mlp_wgrad_tail).  Against the fp32 mirror (the bars of the generic fused path) and against the
+    (bias gradient) x pose (riggs_mlp_wgrad with tail_ch).  Against the fp32 mirror (the bars of the generic fused path) and against the
     generic fused path itself (same kernels with the pose as 96 more operand columns, rounded to 16 bits)."""
     name, net, head, xe = _nets(N)[1]
     assert name == "DeformMLP"
@@ -314,7 +314,7 @@ def test_fused_heads_inside_a_captured_training_iteration():
 
 
 def test_grad_scale_kernels_match_the_formula():
-    """riggs_mlp_grad_scale: 2^floor(log2(1024 / max|g|)) from two launches — against the same formula in torch, for ragged sizes
+    """riggs_amd.mlp.grad_scale (riggs_mlp_cotangent without a g_eff): 2^floor(log2(1024 / max|g|)) from two launches — against the same formula in torch, for ragged sizes
     (the vector loop's tail), a single element, all zeros (clamped at 1e-30), values around the 16-bit subnormal range, and twice in
     a row (the scratch word is left zero)."""
     torch.manual_seed(0)
@@ -329,7 +329,7 @@ def test_grad_scale_kernels_match_the_formula():
             assert ratio in (0.5, 1.0, 2.0), (n, mag, float(sc), float(want))   # (log2 of an exact power of two may round either way)
             if mag > 0:
                 assert 256.0 <= float(amax) * float(sc) <= 2048.0
-    assert all(int(w) == 0 for w in M._ZERO_WORD.values())
+    assert all(int(w[0]) == 0 for w in M._SCRATCH.values())
 
 
 def _sparse_cotangent(N, out_ch, frac, seed=5, mag=3e-8):
@@ -472,14 +472,18 @@ def test_cotangent_kernel_matches_the_formula(N, out_ch):
             assert float(sc) / float(torch.exp2(torch.floor(torch.log2(1024.0 / amax)))) in (0.5, 1.0, 2.0)
             if o is not None:
                 assert abs(float(msq) - float((o * o).mean())) <= 1e-5 * float((o * o).mean())
-    assert all(int(w[0]) == 0 for w in M._L2_SCRATCH.values())
+            if a is g and b is None and s_ is None and o is None:  # g alone: the same scale without a g_eff, g only read
+                g_bits = g.view(torch.int32).clone()
+                assert float(M.grad_scale(g)) == float(sc)
+                assert torch.equal(g.view(torch.int32), g_bits)
+    assert all(int(w[0]) == 0 for w in M._SCRATCH.values())
 
 
 @pytest.mark.parametrize("N,frac", [(1, 1.0), (300, 0.1), (4_097, 0.0), (70_001, 0.1)])
 def test_live_rows_with_the_sigmoid_factor_and_the_scale(N, frac):
     """riggs_mlp_live_rows(sigmoid_out, scale): the rows are tested and gathered on g * s (1 - s) (a saturated output — s exactly 1
     — kills its entry like torch's sigmoid_backward does), and the fp16 gradient scale of that cotangent comes out of the same two
-    launches: equal to riggs_mlp_grad_scale on the materialised product."""
+    launches: equal to riggs_amd.mlp.grad_scale on the materialised product."""
     name, net, head, xe = _nets(N)[0]
     pk = M.FusedHead(net.linear, head, xe.shape[1], net.skips[0])._packed()
     xb = M.embed_bf16(pk, xe)
@@ -764,7 +768,7 @@ def test_rows_past_the_device_count_are_never_read(fmt):
             gwo, gbo = torch.full((pk.out_ch, 256), fill, device=dev), torch.full((pk.out_ch,), fill, device=dev)
             gwp = (C.c_void_p * D)(*[t.data_ptr() for t in gw])
             gbp = (C.c_void_p * D)(*[gb[l].data_ptr() for l in range(D)])
-            L.check(lib.riggs_mlp_wgrad(N, pk.in_ch, pk.out_ch, D, pk.skip, xb.data_ptr(), acts_w.data_ptr(), dpre_w.data_ptr(), g.data_ptr(),
+            L.check(lib.riggs_mlp_wgrad(N, pk.in_ch, 0, None, pk.out_ch, D, pk.skip, xb.data_ptr(), acts_w.data_ptr(), dpre_w.data_ptr(), g.data_ptr(),
                                         L.ptr(sc), ws.data_ptr(), nbytes, gwp, gbp, gwo.data_ptr(), gbo.data_ptr(), n_dev.data_ptr(),
                                         pk.fp16, L.stream_ptr()), "riggs_mlp_wgrad")
             res[fill == 0] = dict(acts=acts, masks=masks, out=out, dpre=dpre, dbp=dbp, grads=gw + [gb, gwo, gbo])

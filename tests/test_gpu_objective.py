@@ -1,5 +1,5 @@
 """-m gpu: the stage-2 objective's two regularisers (train_rig.py:446-456 template-offsets L2, :474-482 template_fixed) as
-cotangents INSIDE the backward launches — ``riggs_mlp_l2_grad_scale`` (the fused DeformMLP's gradient-scale launches) and
+cotangents INSIDE the backward launches — ``riggs_mlp_cotangent`` (the fused DeformMLP's gradient-scale launches) and
 ``riggs_pose_mlp_backward_fk`` (the PoseMLP's backward) — against the golden recorded from the reference's own
 ``render_and_cal_loss`` (tests/golden/objective_tree8_n48.npz, both cameras), and the captured training iteration with the terms
 on against the same objective composed in torch on the same models (what an unmodified train_rig.py gets through autograd)."""
@@ -30,19 +30,19 @@ def test_l2_cotangent_kernel_reproduces_the_reference_gradient_and_value(tag):
     mean_sq = torch.zeros(1, device="cuda")
     want = _t(tag + "_g_template_offsets")
     # alone (the reference's T.grad: the offsets enter the golden's objective through the L2 only) ...
-    g_eff, scale = M.l2_grad_scale(torch.zeros_like(T), T, coef, mean_sq)
+    g_eff, scale = M.cotangent(torch.zeros_like(T), None, None, None, T, coef, mean_sq)
     assert float((g_eff - want).abs().max()) <= 1e-6 * float(want.abs().max())
     assert abs(float(mean_sq) - float(OBJ[tag + "_template_offsets_loss"])) <= 1e-6 * float(mean_sq)
     amax = float(g_eff.abs().max())
     assert float(torch.log2(scale).frac()) == 0.0 and 256.0 <= amax * float(scale) <= 2048.0
     # ... and on top of a cotangent arriving from the render (d_xyz = skinning + offsets: the same rows)
     g = _t(tag + "_g_d_xyz")
-    g_eff, _ = M.l2_grad_scale(g, T, coef, None)
+    g_eff, _ = M.cotangent(g, None, None, None, T, coef, None)
     assert float((g_eff - (g + want)).abs().max()) <= 1e-6 * float((g + want).abs().max())
     # ragged sizes (the vector loop's tail)
     for n in (1, 5, 1023, 4099):
-        a, b = torch.randn(n, device="cuda"), torch.randn(n, device="cuda")
-        ge, _ = M.l2_grad_scale(a, b, coef, mean_sq)
+        a, b = torch.randn(n, 1, device="cuda"), torch.randn(n, 1, device="cuda")
+        ge, _ = M.cotangent(a, None, None, None, b, coef, mean_sq)
         assert torch.allclose(ge, a + coef * b, rtol=1e-6, atol=1e-7) and abs(float(mean_sq) - float((b * b).mean())) <= 1e-5 * float((b * b).mean())
 
 

@@ -161,7 +161,7 @@ def test_library_exports_the_label_entry_and_sizes_the_node_tile_from_the_frames
     assert all(4 * F * lib.riggs_node_semantic_tile(F) <= 64 * 1024 for F in range(1, 1025))
     assert lib.riggs_node_semantic_tile(0) == 0 and lib.riggs_node_semantic_tile(1025) == 0
     assert L.CONSTANTS["RIGGS_SEMANTIC_MAX_FRAMES"] == 1024 and L.CONSTANTS["RIGGS_SEMANTIC_MAX_NODES"] == 65536
-    assert L.CONSTANTS["RIGGS_SEMANTIC_CAMERA_WORDS"] == 24 and L.ABI_VERSION == 101
+    assert L.CONSTANTS["RIGGS_SEMANTIC_CAMERA_WORDS"] == 24 and L.ABI_VERSION == 102
     for F, M in ((0, 4), (1025, 4), (4, 0), (4, 65537)):
         assert lib.riggs_node_semantic_labels(F, M, None, None, None, None, None) != 0 and b"1 <= F <= 1024" in lib.riggs_last_error()
     assert lib.riggs_node_semantic_labels(4, 4, None, None, None, None, None) != 0 and b"NULL" in lib.riggs_last_error()

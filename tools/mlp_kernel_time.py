@@ -10,6 +10,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from riggs_amd import mlp as M  # noqa: E402
 from riggs_amd.skeleton import DeformMLP, WeightMLP  # noqa: E402
+from tests import mlp_ref as R  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 300000
 torch.manual_seed(0)
@@ -51,7 +52,7 @@ for name, net, head, xb, tail in (("WeightMLP", wm, wm.weight_predict, xb64, Non
     t_bwd_b = timed(lambda: M.backward_data(p, g, masks, sc))
     dpre, db = M.backward_data(p, g, masks, sc)
     t_wg = timed(lambda: M.param_grads(p, xb, acts, dpre, g, sc, tail=tail))
-    t_lib = timed(lambda: M.library_param_grads(p, xb, acts, dpre, db, g, sc)) if not n_tail else float("nan")
+    t_lib = timed(lambda: R.library_param_grads(p, xb, acts, dpre, db, g, sc)) if not n_tail else float("nan")
     gb = (2 * (p.depth - 1) * N * 512 + 2 * N * (512 + 2 * p.in_pad) + N * (512 + 64)) / 1e9
     print("%s N=%d: forward %.3f ms (%.0f TFLOP/s; %.3f ms without the activation / mask stores), data gradient %.3f ms (%.0f TFLOP/s)"
           % (name, N, t_fwd, flops / t_fwd / 1e9, t_inf, t_bwd, flops / t_bwd / 1e9))
