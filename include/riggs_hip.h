@@ -1263,6 +1263,43 @@ int riggs_ik_solve(int32_t B, int32_t J, int32_t E, const float* joints, const i
                    int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
                    riggs_stream stream);
 
+/* =====================================================================
+ * Whole-skeleton pose fitting (csrc/fit.hip; riggs_amd/pose_edit.py: fit_pose): EVERY joint may have a target position, which the
+ * dual form of riggs_ik_solve (a 3E x 3E factorisation on one wave) cannot carry.  Levenberg-Marquardt (Levenberg 1944, Marquardt
+ * 1963) with Buss & Kim's clamped target step, the damped normal equations solved matrix-free by Jacobi-preconditioned conjugate
+ * gradients (Hestenes & Stiefel 1952); restated from the published methods, tests/fit_ref.py is the NumPy restatement.  Added
+ * symbol: RIGGS_ABI_VERSION is unchanged.
+ *
+ * joints, parents, B, J, local_rot_in, global_trans_in, locked, damping, max_step, relative and the outputs are riggs_ik_solve's.
+ * targets (B,J,3) and weights (B,J) or NULL (all 1): a weight <= 0 (or NaN) means that the joint has no target; its target is
+ * never read (a NaN there changes nothing).  *extent (device float, > 0) is ALWAYS required: the translation unknown is
+ * tau' = tau / extent, so that all unknowns carry length units.  cg_steps >= 1.
+ * `iterations` >= 0 steps of (s_h = sqrt(w_h), 0 without target; piv_a = posed_vp(a), the root's own position; a subtree
+ * includes its root; positions relative to the posed root, pc = posed - posed_0, which changes neither operator):
+ *   1  forward kinematics; r_h = s_h (target_h - posed_h, shortened to max_step)
+ *   2  J p:    W_j = W_vp(j) + omega_j (a locked joint's omega is 0), C_j = C_vp(j) + omega_j x piv_j,
+ *              u_h = s_h ((W_h x pc_h - C_h) + extent tau')
+ *      J^T u:  F_a = sum_subtree s_h u_h, M_a = sum_subtree pc_h x (s_h u_h), g_a = M_a - piv_a x F_a (locked: 0),
+ *              g_tau' = extent F_0;  A = J^T J + damping^2 I;  a parent adds its children in descending index
+ *   3  Minv_a = 1 / (2/3 d_a + damping^2), d_a = sum_subtree s_h^2 |pc_h - piv_a|^2 = max((S2 - 2 piv_a . S1) + |piv_a|^2 S0, 0)
+ *      from the subtree moments S0, S1, S2 of s^2, s^2 pc, s^2 |pc|^2 ABOUT THE POSED ROOT (every term is then within one rig
+ *      extent of the others, wherever global_trans is);  Minv_tau' = 1 / (extent^2 S0_0 + damping^2)
+ *   4  cg_steps steps of preconditioned conjugate gradients from x = 0 on A x = J^T r.  Before a step it ends unless
+ *      r.z > 1e-10 * (r.z at the start), and unless p.Ap > 0: the same decision in every thread.  A dot product is
+ *      (a0 b0 + a1 b1) + a2 b2 per joint, a balanced binary tree over each 64 joints, the (up to four) sums in order, tau' last.
+ *   5  riggs_ik_solve's step 5 with omega_a = x_a; global_trans += extent x_tau' with solve_translation
+ * then one more forward kinematics: d_nodes (B,J,3) and residual (B,J) = |target - posed| where the joint has a target, else 0.
+ * A locked joint keeps its quaternion bit for bit, as does a joint whose subtree holds no target.
+ * One workgroup per problem, all iterations in ONE launch on `stream` (J <= 64: one wave; else 256 threads); no float atomics:
+ * the same inputs give the same bits, and a problem's result does not depend on the rest of the batch.  Does not allocate, read
+ * back or synchronise: legal inside a stream capture.
+ * ===================================================================== */
+int riggs_fit_pose(int32_t B, int32_t J, const float* joints, const int32_t* parents, const float* local_rot_in,
+                   const float* global_trans_in, const float* targets, const float* weights, const uint8_t* locked,
+                   int32_t iterations, int32_t cg_steps, float damping, float max_step, const float* extent, int32_t relative,
+                   int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
+                   riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

@@ -48,6 +48,7 @@ SOURCES = {
     "hashgrid.hip": ["-ffp-contract=off"],  # (pos = fmaf(scale, x, 0.5) is written as an explicit fma: the oracle's position, bit for bit)
     "semantic.hip": ["-ffp-contract=off"],  # (pinhole.h: the pixel skel_loss.hip sees for the same node)
     "ik.hip": ["-ffp-contract=off"],  # (tests/ik_ref.py rounds every operation: its float32 form is the yardstick for this kernel's rounding)
+    "fit.hip": ["-ffp-contract=off"],  # (tests/fit_ref.py rounds every operation, as ik_ref.py does for ik.hip)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -452,4 +452,82 @@ __device__ __forceinline__ void fk_block_sweep(int J, const FkIn& in, FkWide& f,
   }
 }
 
+// ---- sums over the tree, for a caller whose operator is a sum along root-to-joint paths and its transpose a sum over subtrees
+// (fit.hip: the Jacobian of the chain and its transpose).  They run on the topology an earlier fk_wave_forward / fk_block_forward
+// left in `f` (`sh`): the same levels, the same children, the same order.  Call with all lanes (threads) of the wave (workgroup).
+// fk_*_prefix:  v_j <- v_vp(j) + v_j level by level from the root: v_j becomes the sum over the path root .. j.
+// fk_*_subtree: v_a <- v_a + the finished sums of a's children in descending child index, deepest level first (the order of the
+// sequential sweep i = J - 1 .. 1 and of fk_*_backward): v_a becomes the sum over a's subtree, a included.
+template <int N>
+__device__ __forceinline__ void fk_wave_prefix(const FkLane& f, float (&v)[N]) {
+  for (int l = 1; l <= f.maxlev; l++) {
+#pragma unroll
+    for (int e = 0; e < N; e++) {
+      const float t = fk_lane_get(v[e], f.par);
+      if (f.lev == l) v[e] = t + v[e];
+    }
+  }
+}
+template <int N>
+__device__ __forceinline__ void fk_wave_subtree(int J, const FkLane& f, float (&v)[N]) {
+  const int j = threadIdx.x & 63;
+  for (int l = f.maxlev - 1; l >= 0; l--) {
+    unsigned long long km = (j < J && f.lev == l) ? f.kids : 0ull;
+    while (__builtin_amdgcn_ballot_w64(km != 0ull) != 0ull) {
+      const bool has = km != 0ull;
+      const int i = has ? 63 - __builtin_clzll(km) : j;  // descending child index
+#pragma unroll
+      for (int e = 0; e < N; e++) {
+        const float t = fk_lane_get(v[e], i);
+        if (has) v[e] += t;
+      }
+      if (has) km &= ~(1ull << i);
+    }
+  }
+}
+// ... over the block, through `buf` (MAX_J_WIDE rows of at least N floats in LDS): ONE barrier per level.  The first write of a
+// call lands behind the last read of the call before it only if a barrier lies between the two calls: the caller's business
+// (fit.hip: a dot product's reduction, or the other sweep, always does).  fk_block_prefix leaves every row of `buf` final behind
+// its last barrier; rows >= J hold what their threads passed in.
+template <int N, int S>
+__device__ __forceinline__ void fk_block_prefix(int J, const FkWide& f, float (*buf)[S], float (&v)[N]) {
+  static_assert(N <= S, "fk_block_prefix: the row is too short");
+  const int j = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < N; e++) buf[j][e] = v[e];
+  __syncthreads();
+  for (int l = 1; l <= f.maxlev; l++) {
+    if (j < J && f.lev == l) {
+#pragma unroll
+      for (int e = 0; e < N; e++) { v[e] = buf[f.par][e] + v[e]; buf[j][e] = v[e]; }
+    }
+    __syncthreads();
+  }
+}
+template <int N, int S>
+__device__ __forceinline__ void fk_block_subtree(int J, const FkWide& f, const FkWideShared& sh, float (*buf)[S], float (&v)[N]) {
+  static_assert(N <= S, "fk_block_subtree: the row is too short");
+  const int j = threadIdx.x;
+  const bool on = j < J;
+  for (int l = f.maxlev - 1; l >= 0; l--) {
+    if (on && f.lev == l + 1) {
+#pragma unroll
+      for (int e = 0; e < N; e++) buf[j][e] = v[e];
+    }
+    __syncthreads();
+    if (on && f.lev == l) {
+      for (int w = FK_WIDE_WORDS - 1; w >= 0; w--) {
+        uint32_t km = sh.kids[j][w];
+        while (km != 0u) {
+          const int b = 31 - __builtin_clz(km);  // descending child index
+          const int i = 32 * w + b;
+#pragma unroll
+          for (int e = 0; e < N; e++) v[e] += buf[i][e];
+          km &= ~(1u << b);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace riggs

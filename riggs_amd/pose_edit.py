@@ -8,7 +8,9 @@ NumPy, scipy and two read-backs per mouse event; here it is torch ops that never
 
 ``solve_ik`` is what the reference lacks: drag up to 8 end effectors and let the chain follow — damped least squares (Wampler
 1986) with Buss & Kim's clamped target step on the rig's own kinematics, every iteration inside ONE launch of csrc/ik.hip
-(include/riggs_hip.h: riggs_ik_solve; tests/ik_ref.py is the NumPy restatement).  Inference only."""
+(include/riggs_hip.h: riggs_ik_solve; tests/ik_ref.py is the NumPy restatement).  ``fit_pose`` gives EVERY joint a target
+(a reference skeleton, a frame of a clip of joint positions): Levenberg-Marquardt with matrix-free preconditioned conjugate
+gradients in ONE launch of csrc/fit.hip (riggs_fit_pose; tests/fit_ref.py).  Inference only."""
 from __future__ import annotations
 
 import numpy as np
@@ -150,6 +152,62 @@ def _rig(skeleton):
     return L.require_cuda_f32("joints", joints, (None, 3)), skeleton._parents_dev(joints.device)
 
 
+def _problem(name, skeleton, pose, locked, iterations, damping, max_step):
+    """What ``solve_ik`` and ``fit_pose`` share in front of their own arguments: the rig, the pose, ``locked``, and the host
+    values ``damping`` / ``max_step`` with the ``relative`` mask of their defaults (0.05 and 0.5 times the rig's extent).
+    -> (joints, parents, J, q, gt (n, 3), locked, damping, max_step, relative)."""
+    joints, parents = _rig(skeleton)
+    dev, J = joints.device, int(joints.shape[0])
+    if not 1 <= J <= MAX_JOINTS:
+        raise L.RiggsHipError("%s: %d joints, 1 to %d are supported" % (name, J, MAX_JOINTS))
+    q = L.require_cuda_f32("local_rotation", pose["local_rotation"].detach())
+    if q.dim() not in (2, 3) or tuple(q.shape[-2:]) != (J, 4):
+        raise L.RiggsHipError("local_rotation has shape %s, expected (%d, 4) or (B, %d, 4)" % (tuple(q.shape), J, J))
+    gt = L.require_cuda_f32("global_trans", pose["global_trans"].detach())
+    if locked is not None:
+        locked = torch.as_tensor(locked).to(dev)
+        if tuple(locked.shape) != (J,):
+            raise L.RiggsHipError("locked has shape %s, expected (%d,)" % (tuple(locked.shape), J))
+        locked = (locked != 0).to(torch.uint8).contiguous()
+    if int(iterations) < 0:
+        raise L.RiggsHipError("%s: iterations >= 0" % name)
+    relative = 0
+    if damping is None:
+        damping, relative = 0.05, relative | 1
+    elif not float(damping) > 0:
+        raise L.RiggsHipError("%s: damping must be > 0, got %r" % (name, damping))
+    if max_step is None:
+        max_step, relative = 0.5, relative | 2
+    elif not float(max_step) >= 0:
+        raise L.RiggsHipError("%s: max_step must be >= 0, got %r" % (name, max_step))
+    return joints, parents, J, q, gt.reshape(-1, 3), locked, float(damping), float(max_step), relative
+
+
+def _batch(name, q, gt, per_problem):
+    """The batch: what has a leading dimension names B, the rest is shared.  ``per_problem``: (tensor or None, its number of
+    dimensions when batched) of the caller's own arguments.  -> (B, batched, full) with ``full(t, tail)`` the (B, *tail) contiguous
+    form of ``t``: a view where the tensor already is one, so a graph replay sees in-place changes."""
+    named = [(q, 3)] + list(per_problem)
+    batched = any(t is not None and t.dim() == d for t, d in named) or gt.shape[0] > 1
+    sizes = {int(t.shape[0]) for t, d in named + [(gt, 2)] if t is not None and t.dim() == d}
+    sizes.discard(1)
+    if len(sizes) > 1:
+        raise L.RiggsHipError("%s: the arguments name different batch sizes %s" % (name, sorted(sizes)))
+    B = sizes.pop() if sizes else 1
+    if gt.numel() not in (3, 3 * B):
+        raise L.RiggsHipError("global_trans has shape %s, expected (1, 3) or (%d, 3)" % (tuple(gt.shape), B))
+
+    def full(t, tail):
+        return t.reshape((-1,) + tail).expand((B,) + tail).contiguous()
+    return B, batched, full
+
+
+def _solution(batched, q_out, gt_out, d_nodes, residual):
+    if batched:
+        return {"local_rotation": q_out, "global_trans": gt_out, "d_nodes": d_nodes, "residual": residual}
+    return {"local_rotation": q_out[0], "global_trans": gt_out, "d_nodes": d_nodes[0], "residual": residual[0]}
+
+
 @torch.no_grad()
 def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterations=16, damping=None, max_step=None,
              solve_translation=False):
@@ -157,7 +215,8 @@ def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterat
 
     ``skeleton``: a ``SkeletonWarp`` or ``(joints (J, 3), parents (J,))``, 1 <= J <= 256.  ``pose``: the dict ``deform_by_pose`` /
     ``get_pose_info`` use — ``local_rotation`` (J, 4) or (B, J, 4), un-normalised wxyz; ``global_trans`` (1, 3) or (B, 3).
-    ``handles``: (E,) or (B, E) joint indices, 1 <= E <= 8; ``targets`` (..., E, 3); ``weights`` (..., E), a weight <= 0 switches
+    ``handles``: (E,) or (B, E) joint indices, 1 <= E <= 8 (targets for more joints, up to every one: ``fit_pose``); ``targets``
+    (..., E, 3); ``weights`` (..., E), a weight <= 0 switches
     its handle off (so the number of live handles changes without a new shape); ``locked`` (J,) bool: joints that keep their
     rotation.  Unbatched arguments are shared by the B problems.  ``damping`` (> 0) and ``max_step`` default to 0.05 and 0.5 times
     ``rig_extent(joints)``, which stays on the device.  ``solve_translation``: ``global_trans`` is solved for as well.
@@ -172,14 +231,8 @@ def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterat
     replayed after ``targets`` / ``handles`` / ``weights`` (device tensors) were changed in place.  Handle indices given on the
     host (a list, an array, a CPU tensor) are checked here; on the device they are not read: the kernel switches off a handle
     outside [0, J) and reports NaN as its residual."""
-    joints, parents = _rig(skeleton)
-    dev, J = joints.device, int(joints.shape[0])
-    if not 1 <= J <= MAX_JOINTS:
-        raise L.RiggsHipError("solve_ik: %d joints, 1 to %d are supported" % (J, MAX_JOINTS))
-    q = L.require_cuda_f32("local_rotation", pose["local_rotation"].detach())
-    if q.dim() not in (2, 3) or tuple(q.shape[-2:]) != (J, 4):
-        raise L.RiggsHipError("local_rotation has shape %s, expected (%d, 4) or (B, %d, 4)" % (tuple(q.shape), J, J))
-    gt = L.require_cuda_f32("global_trans", pose["global_trans"].detach())
+    joints, parents, J, q, gt, locked, damping, max_step, relative = _problem("solve_ik", skeleton, pose, locked, iterations, damping, max_step)
+    dev = joints.device
     if torch.is_tensor(handles) and handles.is_cuda:
         h = handles
     else:
@@ -197,37 +250,8 @@ def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterat
         weights = L.require_cuda_f32("weights", weights.detach())
         if weights.dim() not in (1, 2) or weights.shape[-1] != E:
             raise L.RiggsHipError("weights has shape %s, expected (..., %d)" % (tuple(weights.shape), E))
-    if locked is not None:
-        locked = torch.as_tensor(locked).to(dev)
-        if tuple(locked.shape) != (J,):
-            raise L.RiggsHipError("locked has shape %s, expected (%d,)" % (tuple(locked.shape), J))
-        locked = (locked != 0).to(torch.uint8).contiguous()
-    if int(iterations) < 0:
-        raise L.RiggsHipError("solve_ik: iterations >= 0")
-    relative = 0
-    if damping is None:
-        damping, relative = 0.05, relative | 1
-    elif not float(damping) > 0:
-        raise L.RiggsHipError("solve_ik: damping must be > 0, got %r" % (damping,))
-    if max_step is None:
-        max_step, relative = 0.5, relative | 2
-    elif not float(max_step) >= 0:
-        raise L.RiggsHipError("solve_ik: max_step must be >= 0, got %r" % (max_step,))
     extent = rig_extent(joints) if relative else None
-
-    # the batch: what has a leading dimension names B, the rest is shared
-    gt = gt.reshape(-1, 3)
-    batched = q.dim() == 3 or h.dim() == 2 or targets.dim() == 3 or (weights is not None and weights.dim() == 2) or gt.shape[0] > 1
-    sizes = {int(t.shape[0]) for t, d in ((q, 3), (h, 2), (targets, 3), (weights, 2), (gt, 2)) if t is not None and t.dim() == d}
-    sizes.discard(1)
-    if len(sizes) > 1:
-        raise L.RiggsHipError("solve_ik: the arguments name different batch sizes %s" % sorted(sizes))
-    B = sizes.pop() if sizes else 1
-    if gt.numel() not in (3, 3 * B):
-        raise L.RiggsHipError("global_trans has shape %s, expected (1, 3) or (%d, 3)" % (tuple(gt.shape), B))
-
-    def full(t, tail):  # (B, *tail) contiguous: a view where the tensor already is, so a graph replay sees in-place changes
-        return t.reshape((-1,) + tail).expand((B,) + tail).contiguous()
+    B, batched, full = _batch("solve_ik", q, gt, [(h, 2), (targets, 3), (weights, 2)])
     qb, gtb, hb, tb = full(q, (J, 4)), full(gt, (3,)), full(h.to(torch.int32), (E,)), full(targets, (E, 3))
     wb = None if weights is None else full(weights, (E,))
     f32 = dict(dtype=torch.float32, device=dev)
@@ -235,9 +259,55 @@ def solve_ik(skeleton, pose, handles, targets, weights=None, locked=None, iterat
     d_nodes, residual = torch.empty(B, J, 3, **f32), torch.empty(B, E, **f32)
     with torch.cuda.device(dev):
         L.check(L.lib().riggs_ik_solve(B, J, E, joints.data_ptr(), parents.data_ptr(), qb.data_ptr(), gtb.data_ptr(), hb.data_ptr(),
-                                       tb.data_ptr(), L.ptr(wb), L.ptr(locked), int(iterations), float(damping), float(max_step),
+                                       tb.data_ptr(), L.ptr(wb), L.ptr(locked), int(iterations), damping, max_step,
                                        L.ptr(extent), relative, int(bool(solve_translation)), q_out.data_ptr(), gt_out.data_ptr(),
                                        d_nodes.data_ptr(), residual.data_ptr(), L.stream_ptr()), "riggs_ik_solve")
-    if batched:
-        return {"local_rotation": q_out, "global_trans": gt_out, "d_nodes": d_nodes, "residual": residual}
-    return {"local_rotation": q_out[0], "global_trans": gt_out, "d_nodes": d_nodes[0], "residual": residual[0]}
+    return _solution(batched, q_out, gt_out, d_nodes, residual)
+
+
+@torch.no_grad()
+def fit_pose(skeleton, pose, targets, weights=None, locked=None, iterations=32, cg_steps=8, damping=None, max_step=None,
+             solve_translation=False):
+    """Turn the joints of ``pose`` so that EVERY joint reaches its own target: matching the rig to a reference skeleton, turning
+    a clip of joint positions into a pose track, re-posing a rig whose rest joints were extracted anew.
+
+    ``skeleton``, ``pose``, ``locked``, ``damping``, ``max_step``, ``solve_translation`` and the batching are ``solve_ik``'s.
+    ``targets``: (J, 3) or (B, J, 3), one per joint; ``weights`` (J,) or (B, J), all 1 by default: a weight <= 0 means that the
+    joint has no target, and its entry of ``targets`` is never read (a NaN there changes no bit of the result).
+    ``cg_steps`` (>= 1): conjugate-gradient steps per iteration.  More steps than joints gain nothing, and they make the twist
+    about a bone, which no position observes, depend on the order of the sums: rotations then differ by 1e-2 between
+    implementations while the positions agree.  Keep ``cg_steps <= J``.
+
+    The method: Levenberg-Marquardt on the rig's kinematics with the clamped target step, the damped normal equations solved
+    matrix-free by Jacobi-preconditioned conjugate gradients, where the Jacobian of the tree and its transpose are two sweeps
+    over its levels (include/riggs_hip.h states the iteration, tests/fit_ref.py restates it in NumPy).
+
+    Returns ``{'local_rotation', 'global_trans', 'd_nodes', 'residual'}`` as ``solve_ik`` does, with ``residual`` (..., J):
+    ``|target - posed joint|`` where the weight is > 0, and 0 elsewhere.  A (B, J, 4) result is a track for ``deform_sequence``.
+
+    One launch of csrc/fit.hip, allocations through torch only, nothing read back: the call can be captured in a
+    ``torch.cuda.graph`` (with ``deform_by_pose`` behind it) and replayed after ``targets`` / ``weights`` changed in place."""
+    if int(cg_steps) < 1:
+        raise L.RiggsHipError("fit_pose: cg_steps must be >= 1, got %r" % (cg_steps,))
+    joints, parents, J, q, gt, locked, damping, max_step, relative = _problem("fit_pose", skeleton, pose, locked, iterations, damping, max_step)
+    dev = joints.device
+    targets = L.require_cuda_f32("targets", targets.detach())
+    if targets.dim() not in (2, 3) or tuple(targets.shape[-2:]) != (J, 3):
+        raise L.RiggsHipError("targets has shape %s, expected (%d, 3) or (B, %d, 3)" % (tuple(targets.shape), J, J))
+    if weights is not None:
+        weights = L.require_cuda_f32("weights", weights.detach())
+        if weights.dim() not in (1, 2) or weights.shape[-1] != J:
+            raise L.RiggsHipError("weights has shape %s, expected (%d,) or (B, %d)" % (tuple(weights.shape), J, J))
+    extent = rig_extent(joints)  # (always: the translation unknown is scaled by it)
+    B, batched, full = _batch("fit_pose", q, gt, [(targets, 3), (weights, 2)])
+    qb, gtb, tb = full(q, (J, 4)), full(gt, (3,)), full(targets, (J, 3))
+    wb = None if weights is None else full(weights, (J,))
+    f32 = dict(dtype=torch.float32, device=dev)
+    q_out, gt_out = torch.empty(B, J, 4, **f32), torch.empty(B, 3, **f32)
+    d_nodes, residual = torch.empty(B, J, 3, **f32), torch.empty(B, J, **f32)
+    with torch.cuda.device(dev):
+        L.check(L.lib().riggs_fit_pose(B, J, joints.data_ptr(), parents.data_ptr(), qb.data_ptr(), gtb.data_ptr(), tb.data_ptr(),
+                                       L.ptr(wb), L.ptr(locked), int(iterations), int(cg_steps), damping, max_step,
+                                       extent.data_ptr(), relative, int(bool(solve_translation)), q_out.data_ptr(),
+                                       gt_out.data_ptr(), d_nodes.data_ptr(), residual.data_ptr(), L.stream_ptr()), "riggs_fit_pose")
+    return _solution(batched, q_out, gt_out, d_nodes, residual)
