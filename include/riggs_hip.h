@@ -728,6 +728,25 @@ int riggs_cnode_backward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t
                          float* g_feature, float* g_motion_mask, float* g_node_trans, float* g_node_rot, float* g_node_scale,
                          float* g_local_rot, float* g_node_radius_log, float* g_node_weight_logit, float* g_nodes_hyper,
                          float* workspace, riggs_stream stream);
+/* ---- Playback of a time track (inference only: no backward exists; ControlNodeWarp.deform_sequence).  Added symbols:
+ * RIGGS_ABI_VERSION is unchanged.
+ * riggs_cnode_sequence_forward: riggs_cnode_forward for T frames over ONE canonical cloud in one launch.  cal_nn_weight does
+ * not depend on time, so a thread scans the nodes for its Gaussian once and keeps its K indices, normalised weights and the K
+ * nodes' xyz in registers (the device code of riggs_cnode_forward: nn_idx and nn_dist equal its bit for bit); then it walks
+ * the frames, gathers its K nodes' records of frame f from node_trans (T,M,3), node_rot (T,M,4), node_scale (T,M,3) and
+ * local_rot (T,M,4; NULL without local_frame) and writes row (f, i) of d_xyz (T,N,3), d_rot (T,N,4), d_scale (T,N,3):
+ * frame-major, a frame is contiguous.  nn_idx, nn_weight, nn_dist (N,K) are written once.  Limits and flags are those of
+ * riggs_cnode_forward; T M <= 2^29; node_rot, local_rot and d_rot 16-byte aligned (they move as float4).  T = 0 or N = 0: no
+ * launch, the per-Gaussian pointers may be NULL.
+ * riggs_cnode_sequence_pass_frames: the frames the kernel takes per pass — 1: it has no passes, a frame's records are
+ * gathered straight from the (T,M,.) tables, which stay in L2. */
+int riggs_cnode_sequence_forward(int32_t N, int32_t M, int32_t T, int32_t K, int32_t hyper, int32_t feat_stride,
+                                 int32_t node_stride, int32_t flags, const float* x, const float* feature,
+                                 const float* motion_mask, const float* nodes, const float* node_radius_log,
+                                 const float* node_weight_logit, const float* node_trans, const float* node_rot,
+                                 const float* node_scale, const float* local_rot, float* d_xyz, float* d_rot, float* d_scale,
+                                 int32_t* nn_idx, float* nn_weight, float* nn_dist, riggs_stream stream);
+int32_t riggs_cnode_sequence_pass_frames(int32_t M, int32_t flags);
 
 /* =====================================================================
  * Stage-1 node regularisers (csrc/node_reg.hip): ControlNodeWarp.arap_loss / elastic_loss / acc_loss

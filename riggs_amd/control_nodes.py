@@ -10,8 +10,10 @@ kernel's neighbour lists) and ``skinning=True`` (softmax of a per-Gaussian (N, M
 path, time_utils.py:1165-1213: an as-rigid-as-possible re-posing of the Gaussians around dragged nodes, under ``no_grad``) in
 torch ops on top of the kernel's blend — it runs per mouse event, not per training step.  The node network
 (``self.network``: nodes, t -> per-node attributes; 512-1024 rows, time_utils.py:990-1002) is a torch module supplied by the
-caller: ``riggs_amd.node_network.DeformNetwork`` (csrc/node_mlp.hip) for the shipped flags, ``riggs_amd.hash_network.HashDeformNetwork``
-(csrc/hashgrid.hip) with ``use_hash=True``, or any module ``(x, t) -> dict``.
+caller; ``deform_sequence`` evaluates a whole time track over one cloud — one network call, one blend launch whose scan of the
+nodes runs once per track (inference only).  Networks: ``riggs_amd.node_network.DeformNetwork`` (csrc/node_mlp.hip) for the
+shipped flags, ``riggs_amd.hash_network.HashDeformNetwork`` (csrc/hashgrid.hip) with ``use_hash=True``, or any module
+``(x, t) -> dict``.
 No CPU / eager fallback.
 """
 from __future__ import annotations
@@ -81,11 +83,9 @@ class _ControlNodeBlend(torch.autograd.Function):
         return (None, g_feature, g_mask, g_nodes, g_radius, g_weight, g_trans, g_nrot, g_nscale, g_local, None, None, None)
 
 
-def control_node_blend(x, feature, motion_mask, nodes, _node_radius, _node_weight, node_attrs, K=3, hyper_dim=0,
-                       local_frame=False, d_rot_as_res=True):
-    """The per-Gaussian part of ``ControlNodeWarp.forward`` (time_utils.py:1138-1191) given the nodes' attributes
-    ``node_attrs = {'d_xyz', 'd_rotation', 'd_scaling', 'local_rotation'}``; returns the reference's dict (without ``d_nodes``)
-    plus ``nn_idx`` (int32), ``nn_weight``, ``nn_dist`` of ``cal_nn_weight`` (:934-964)."""
+def _blend_inputs(x, feature, motion_mask, nodes, _node_radius, _node_weight, hyper_dim, local_frame, d_rot_as_res):
+    """What the blend kernels take besides the nodes' attributes, checked: ``(x, feature or None, mask (N,) or None, nodes,
+    radius, weight or None, hyper, flags)``."""
     x = L.require_cuda_f32("x", x.detach(), (x.shape[0], 3)).contiguous()
     nodes = L.require_cuda_f32("nodes", nodes).contiguous()
     M = nodes.shape[0]
@@ -103,14 +103,62 @@ def control_node_blend(x, feature, motion_mask, nodes, _node_radius, _node_weigh
             raise NotImplementedError("motion_mask must be per Gaussian (N, 1) or 1")
     elif motion_mask is not None and float(motion_mask) != 1.0:
         raise NotImplementedError("motion_mask must be per Gaussian (N, 1) or 1")
-    f = lambda name, t, w: L.require_cuda_f32(name, t, (M, w)).contiguous()  # noqa: E731
-    trans, rot, scale = f("d_xyz", node_attrs["d_xyz"], 3), f("d_rotation", node_attrs["d_rotation"], 4), f("d_scaling", node_attrs["d_scaling"], 3)
-    local_rot = f("local_rotation", node_attrs["local_rotation"], 4) if local_frame else None
     radius = L.require_cuda_f32("_node_radius", _node_radius, (M,)).contiguous()
     weight = L.require_cuda_f32("_node_weight", _node_weight).reshape(M).contiguous() if _node_weight is not None else None
     flags = (LOCAL_FRAME if local_frame else 0) | (ROT_AS_RES if d_rot_as_res else 0)
+    return x, feature, mask, nodes, radius, weight, hyper, flags
+
+
+def control_node_blend(x, feature, motion_mask, nodes, _node_radius, _node_weight, node_attrs, K=3, hyper_dim=0,
+                       local_frame=False, d_rot_as_res=True):
+    """The per-Gaussian part of ``ControlNodeWarp.forward`` (time_utils.py:1138-1191) given the nodes' attributes
+    ``node_attrs = {'d_xyz', 'd_rotation', 'd_scaling', 'local_rotation'}``; returns the reference's dict (without ``d_nodes``)
+    plus ``nn_idx`` (int32), ``nn_weight``, ``nn_dist`` of ``cal_nn_weight`` (:934-964)."""
+    x, feature, mask, nodes, radius, weight, hyper, flags = _blend_inputs(x, feature, motion_mask, nodes, _node_radius, _node_weight,
+                                                                          hyper_dim, local_frame, d_rot_as_res)
+    M = nodes.shape[0]
+    f = lambda name, t, w: L.require_cuda_f32(name, t, (M, w)).contiguous()  # noqa: E731
+    trans, rot, scale = f("d_xyz", node_attrs["d_xyz"], 3), f("d_rotation", node_attrs["d_rotation"], 4), f("d_scaling", node_attrs["d_scaling"], 3)
+    local_rot = f("local_rotation", node_attrs["local_rotation"], 4) if local_frame else None
     d_xyz, d_rot, d_scale, nn_idx, nn_weight, nn_dist = _ControlNodeBlend.apply(
         x, feature, mask, nodes, radius, weight, trans, rot, scale, local_rot, int(K), int(hyper), flags)
+    return {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": d_scale, "d_opacity": None, "d_color": None,
+            "nn_idx": nn_idx, "nn_weight": nn_weight, "nn_dist": nn_dist}
+
+
+def sequence_pass_frames(M: int, flags: int = 0) -> int:
+    """Frames the sequence kernel takes per pass (csrc/cnode.hip); 1: it has no passes."""
+    return int(L.lib().riggs_cnode_sequence_pass_frames(int(M), int(flags)))
+
+
+def control_node_blend_sequence(x, feature, motion_mask, nodes, _node_radius, _node_weight, node_attrs, K=3, hyper_dim=0,
+                                local_frame=False, d_rot_as_res=True):
+    """``control_node_blend`` for T frames over one cloud in ONE launch: ``node_attrs`` holds (T, M, c) tensors, the outputs
+    ``d_xyz`` (T, N, 3), ``d_rotation`` (T, N, 4), ``d_scaling`` (T, N, 3) are frame-major (``out[k][f]`` is contiguous);
+    ``nn_idx`` (int32), ``nn_weight``, ``nn_dist`` (N, K) do not depend on time and are written once — the scan over the nodes
+    runs once per track, not once per frame.  Inference only: no graph, no backward."""
+    with torch.no_grad():
+        x, feature, mask, nodes, radius, weight, hyper, flags = _blend_inputs(x, feature, motion_mask, nodes.detach(), _node_radius.detach(),
+                                                                              None if _node_weight is None else _node_weight.detach(),
+                                                                              hyper_dim, local_frame, d_rot_as_res)
+        N, M, K = x.shape[0], nodes.shape[0], int(K)
+        T = int(node_attrs["d_xyz"].shape[0])
+        def f(name, w):  # (the kernel reads the quaternion tables 16 bytes at a time)
+            t = L.require_cuda_f32(name, node_attrs[name].detach(), (T, M, w)).contiguous()
+            return t if t.data_ptr() % 16 == 0 else t.clone()
+        trans, rot, scale = f("d_xyz", 3), f("d_rotation", 4), f("d_scaling", 3)
+        local_rot = f("local_rotation", 4) if local_frame else None
+        f32 = dict(dtype=torch.float32, device=x.device)
+        d_xyz, d_rot, d_scale = torch.empty(T, N, 3, **f32), torch.empty(T, N, 4, **f32), torch.empty(T, N, 3, **f32)
+        lists = torch.empty if T > 0 else torch.zeros  # (an empty track launches nothing)
+        nn_idx = lists(N, K, dtype=torch.int32, device=x.device)
+        nn_weight, nn_dist = lists(N, K, **f32), lists(N, K, **f32)
+        fs = feature.shape[1] if feature is not None else 0
+        L.check(L.lib().riggs_cnode_sequence_forward(N, M, T, K, hyper, fs, nodes.shape[1], flags, x.data_ptr(), L.ptr(feature),
+                                                     L.ptr(mask), nodes.data_ptr(), radius.data_ptr(), L.ptr(weight), trans.data_ptr(),
+                                                     rot.data_ptr(), scale.data_ptr(), L.ptr(local_rot), d_xyz.data_ptr(),
+                                                     d_rot.data_ptr(), d_scale.data_ptr(), nn_idx.data_ptr(), nn_weight.data_ptr(),
+                                                     nn_dist.data_ptr(), L.stream_ptr()), "riggs_cnode_sequence_forward")
     return {"d_xyz": d_xyz, "d_rotation": d_rot, "d_scaling": d_scale, "d_opacity": None, "d_color": None,
             "nn_idx": nn_idx, "nn_weight": nn_weight, "nn_dist": nn_dist}
 
@@ -639,6 +687,50 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
         gs_t = nodes_t[idx] + torch.einsum("gkab,gkb->gka", R, gs_init[:, None] - cur_node[idx])
         out["d_xyz"] = ((gs_t * w[..., None]).sum(dim=1) - x) * motion_mask
         out["d_rotation_bias"] = ((q_bias[idx] * w[..., None]).sum(dim=1) - rot_bias) * motion_mask + rot_bias
+        return out
+
+    @torch.no_grad()
+    def deform_sequence(self, x, times, feature, motion_mask, animation_d_values=None, node_trans_bias=None, **kwargs):
+        """``forward`` at every time of ``times`` (T,) over one cloud: ONE call of the node network for all T M rows and ONE
+        blend launch (csrc/cnode.hip: cnode_sequence_kernel) in which every Gaussian finds its K nodes and their weights once
+        — they do not depend on time — and then only gathers its nodes' records frame by frame.  Returns ``d_xyz`` (T, N, 3),
+        ``d_rotation`` (T, N, 4), ``d_scaling`` (T, N, 3), ``d_nodes`` (T, M, 3), ``d_opacity`` / ``d_color`` (T, N, .) or None,
+        ``nn_idx``, ``nn_weight``, ``nn_dist`` (N, K) and ``times``; frame-major, so ``out["d_xyz"][f]`` is contiguous and
+        goes into ``render()`` as it is.  ``animation_d_values``: overrides of (T, M, c) per key, applied as ``forward`` applies
+        its own; ``kwargs`` go to the network.
+
+        INFERENCE ONLY: it runs under ``torch.no_grad()``, its outputs carry no graph, ``reg_loss`` and the module's training
+        state are left alone.  ``node_trans_bias`` (the editing path) is per mouse event, not per track: not implemented."""
+        if node_trans_bias is not None:
+            raise NotImplementedError("deform_sequence: node_trans_bias (the editing path) works on one time; use forward()")
+        times = torch.as_tensor(times, dtype=torch.float32, device=self.nodes.device)
+        if times.dim() != 1:
+            raise ValueError("deform_sequence: times must be (T,), got %s" % (tuple(times.shape),))
+        T, M, N = int(times.shape[0]), self.node_num, int(x.shape[0])
+        if T > 0:  # one network call for the T M rows, laid out frame-major for the kernel
+            nd = self.node_deform(t=times[None, :, None].expand(M, T, 1), **kwargs)
+            node_attrs = {k: v.transpose(0, 1).contiguous() for k, v in nd.items() if v is not None and k != "hidden"}
+        else:
+            z = lambda c: torch.zeros(0, M, c, device=self.nodes.device)  # noqa: E731
+            node_attrs = {"d_xyz": z(3), "d_rotation": z(4), "d_scaling": z(3), "local_rotation": z(4), "d_opacity": z(1), "d_color": z(3)}
+        if animation_d_values is not None:
+            for k, v in animation_d_values.items():
+                if v.dim() != 3 or v.shape[0] != T or v.shape[1] != M or (k in node_attrs and v.shape[2] != node_attrs[k].shape[2]):
+                    raise ValueError("deform_sequence: animation_d_values[%r] has shape %s, expected (%d, %d, c)"
+                                     % (k, tuple(v.shape), T, M))
+                node_attrs[k] = v.detach()
+        if self.skinning:  # the dense path: the softmax once, one batched product over the frames
+            out = skinning_blend(feature.detach(), motion_mask, node_attrs, self.d_rot_as_res, self.pred_opacity, self.pred_color)
+        else:
+            nw = self._node_weight if self.with_node_weight else None
+            out = control_node_blend_sequence(x, feature, motion_mask, self.nodes, self._node_radius, nw, node_attrs, K=self.K,
+                                              hyper_dim=self.hyper_dim, local_frame=self.local_frame, d_rot_as_res=self.d_rot_as_res)
+            idx = out["nn_idx"].long()
+            for on, k in ((self.pred_opacity, "d_opacity"), (self.pred_color, "d_color")):  # (time_utils.py:1214-1225), all frames at once
+                if on:
+                    out[k] = (node_attrs[k][:, idx] * out["nn_weight"][None, :, :, None]).sum(dim=2) * motion_mask
+        out["d_nodes"] = self.nodes[None, :, :3].detach() + node_attrs["d_xyz"]
+        out["times"] = times
         return out
 
     def forward(self, x, t, feature, motion_mask, animation_d_values=None, node_trans_bias=None, iteration=0, is_training=True,

@@ -11,7 +11,8 @@
 // 21 + hyper_dim contributions (translation, rotation, scale, dL/dR of the local frame, radius, node weight, hyper coordinates)
 // as a 128-byte row at the entry's sorted position, and one workgroup per node that sums its contiguous rows and applies the
 // node-level chain rules (quaternion -> matrix, exp, sigmoid): five launches, no float atomics.  Forward is issue-bound by the
-// scan (N M (3 + hyper) FMAs); the tables it reads are L2-resident.
+// scan (N M (3 + hyper) FMAs); the tables it reads are L2-resident.  Playback (cnode_sequence_kernel, inference only) runs the
+// scan once for a whole time track and then only gathers and blends per frame: the scan does not depend on time.
 #include "common.h"
 
 namespace riggs {
@@ -73,9 +74,10 @@ __device__ __forceinline__ void cn_kernel_weight(const CNodeArgs& a, int node, f
   nw = a.weight_logit ? 1.0f / (1.0f + expf(-a.weight_logit[node])) : 1.0f;
 }
 
-template <int K, int DP4>
-__global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
-  extern __shared__ float4 s_nodes[];  // (M, DP4) float4: coordinates padded with zeros
+// ---- what cnode_forward_kernel and cnode_sequence_kernel share: the node table in LDS, the scan, the weights, the blend ------
+// (M, DP4) float4 in LDS: the nodes' 3 + hyper coordinates padded with zeros; ends with the workgroup's barrier
+template <int DP4>
+__device__ __forceinline__ void cn_stage_nodes(const CNodeArgs& a, float4* s_nodes) {
   const int D = 3 + a.hyper;
   for (int e = threadIdx.x; e < a.M * DP4; e += 256) {
     const int n = e / DP4, c = e - n * DP4;
@@ -85,24 +87,28 @@ __global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
     s_nodes[e] = make_float4(v[0], v[1], v[2], v[3]);
   }
   __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.N) return;
-  float4 me[DP4];
-  {
-    float v[4 * DP4];
+}
+
+// Gaussian i's coordinates in the table's layout
+template <int DP4>
+__device__ __forceinline__ void cn_load_point(const CNodeArgs& a, int i, float4 (&me)[DP4]) {
+  const int D = 3 + a.hyper;
+  float v[4 * DP4];
 #pragma unroll
-    for (int d = 0; d < 4 * DP4; ++d) v[d] = 0.f;
-    v[0] = a.x[3 * (size_t)i + 0]; v[1] = a.x[3 * (size_t)i + 1]; v[2] = a.x[3 * (size_t)i + 2];
+  for (int d = 0; d < 4 * DP4; ++d) v[d] = 0.f;
+  v[0] = a.x[3 * (size_t)i + 0]; v[1] = a.x[3 * (size_t)i + 1]; v[2] = a.x[3 * (size_t)i + 2];
 #pragma unroll
-    for (int d = 3; d < 4 * DP4; ++d) if (d < D) v[d] = a.feature[(size_t)i * a.feat_stride + (d - 3)];
+  for (int d = 3; d < 4 * DP4; ++d) if (d < D) v[d] = a.feature[(size_t)i * a.feat_stride + (d - 3)];
 #pragma unroll
-    for (int c = 0; c < DP4; ++c) me[c] = make_float4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
-  }
-  float bd[K];
-  int bi[K];
+  for (int c = 0; c < DP4; ++c) me[c] = make_float4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
+}
+
+// the scan: K smallest squared distances (an explicit fmaf chain), ascending, ties to the lowest index
+template <int K, int DP4>
+__device__ __forceinline__ void cn_select(int M, const float4* s_nodes, const float4 (&me)[DP4], float (&bd)[K], int (&bi)[K]) {
 #pragma unroll
   for (int k = 0; k < K; ++k) { bd[k] = 3.0e38f; bi[k] = 0; }
-  for (int j = 0; j < a.M; ++j) {
+  for (int j = 0; j < M; ++j) {
     float d = 0.f;
 #pragma unroll
     for (int c = 0; c < DP4; ++c) {
@@ -112,8 +118,12 @@ __global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
     }
     if (d < bd[K - 1]) cn_insert<K>(bd, bi, d, j);
   }
-  // weights
-  float w[K], vsum = 0.f;
+}
+
+// normalised weights of the K selected nodes
+template <int K>
+__device__ __forceinline__ void cn_weights(const CNodeArgs& a, const int (&bi)[K], const float (&bd)[K], float (&w)[K]) {
+  float vsum = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     float e, nw, r2;
@@ -121,41 +131,161 @@ __global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
     w[k] = e * nw + 1e-7f;
     vsum += w[k];
   }
+#pragma unroll
+  for (int k = 0; k < K; ++k) w[k] = w[k] / vsum;
+}
+
+// a node's record of one frame
+struct CNodeRec { float t[3], q[4], s[3], l[4]; };
+
+__device__ __forceinline__ CNodeRec cn_load_rec(int flags, const float* trans, const float* rot, const float* scale,
+                                                const float* local_rot, int n) {
+  CNodeRec r;
+  r.t[0] = trans[3 * n + 0]; r.t[1] = trans[3 * n + 1]; r.t[2] = trans[3 * n + 2];
+  if (flags & CN_LOCAL_FRAME) { r.l[0] = local_rot[4 * n + 0]; r.l[1] = local_rot[4 * n + 1]; r.l[2] = local_rot[4 * n + 2]; r.l[3] = local_rot[4 * n + 3]; }
+  r.q[0] = rot[4 * n + 0]; r.q[1] = rot[4 * n + 1]; r.q[2] = rot[4 * n + 2]; r.q[3] = rot[4 * n + 3];
+  r.s[0] = scale[3 * n + 0]; r.s[1] = scale[3 * n + 1]; r.s[2] = scale[3 * n + 2];
+  return r;
+}
+
+// the same record with the two quaternions as 16-byte loads (rot and local_rot 16-byte aligned)
+__device__ __forceinline__ CNodeRec cn_load_rec4(int flags, const float* trans, const float* rot, const float* scale,
+                                                 const float* local_rot, int n) {
+  CNodeRec r;
+  r.t[0] = trans[3 * n + 0]; r.t[1] = trans[3 * n + 1]; r.t[2] = trans[3 * n + 2];
+  if (flags & CN_LOCAL_FRAME) {
+    const float4 l = reinterpret_cast<const float4*>(local_rot)[n];
+    r.l[0] = l.x; r.l[1] = l.y; r.l[2] = l.z; r.l[3] = l.w;
+  }
+  const float4 q = reinterpret_cast<const float4*>(rot)[n];
+  r.q[0] = q.x; r.q[1] = q.y; r.q[2] = q.z; r.q[3] = q.w;
+  r.s[0] = scale[3 * n + 0]; r.s[1] = scale[3 * n + 1]; r.s[2] = scale[3 * n + 2];
+  return r;
+}
+
+// a node's record into the ten sums acc = (translation 3, rotation 4, scale 3); nd_ptr: the node's xyz (read with local_frame only)
+__device__ __forceinline__ void cn_blend_node(int flags, const CNodeRec& r, float w, float x0, float x1, float x2,
+                                              const float4* nd_ptr, float (&acc)[10]) {
+  float y0 = r.t[0], y1 = r.t[1], y2 = r.t[2];
+  if (flags & CN_LOCAL_FRAME) {
+    const float q[4] = {r.l[0] + 1.0f, r.l[1], r.l[2], r.l[3]};
+    float R[9];
+    cn_quat_to_mat(q, R);
+    const float4 nd = *nd_ptr;
+    const float r0 = x0 - nd.x, r1 = x1 - nd.y, r2 = x2 - nd.z;
+    y0 += R[0] * r0 + R[1] * r1 + R[2] * r2 + nd.x;
+    y1 += R[3] * r0 + R[4] * r1 + R[5] * r2 + nd.y;
+    y2 += R[6] * r0 + R[7] * r1 + R[8] * r2 + nd.z;
+  }
+  acc[0] += w * y0; acc[1] += w * y1; acc[2] += w * y2;
+  const float bias = (flags & CN_ROT_AS_RES) ? 0.f : 1.f;
+  acc[3] += w * (r.q[0] + bias); acc[4] += w * r.q[1]; acc[5] += w * r.q[2]; acc[6] += w * r.q[3];
+  acc[7] += w * r.s[0]; acc[8] += w * r.s[1]; acc[9] += w * r.s[2];
+}
+
+// the blended sums -> one Gaussian's rows of d_xyz (3), d_rot (4), d_scale (3)
+__device__ __forceinline__ void cn_store_blend(int flags, float (&acc)[10], float x0, float x1, float x2, float m, float* d_xyz,
+                                               float* d_rot, float* d_scale) {
+  if (flags & CN_LOCAL_FRAME) { acc[0] -= x0; acc[1] -= x1; acc[2] -= x2; }
+  d_xyz[0] = acc[0] * m; d_xyz[1] = acc[1] * m; d_xyz[2] = acc[2] * m;
+  if (flags & CN_ROT_AS_RES) {
+    d_rot[0] = acc[3] * m;
+  } else {
+    d_rot[0] = (acc[3] - 1.0f) * m + 1.0f;
+  }
+  d_rot[1] = acc[4] * m; d_rot[2] = acc[5] * m; d_rot[3] = acc[6] * m;
+  d_scale[0] = acc[7] * m; d_scale[1] = acc[8] * m; d_scale[2] = acc[9] * m;
+}
+
+template <int K, int DP4>
+__global__ void __launch_bounds__(256) cnode_forward_kernel(CNodeArgs a) {
+  extern __shared__ float4 s_nodes[];  // (M, DP4) float4: coordinates padded with zeros
+  cn_stage_nodes<DP4>(a, s_nodes);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.N) return;
+  float4 me[DP4];
+  cn_load_point<DP4>(a, i, me);
+  float bd[K];
+  int bi[K];
+  cn_select<K, DP4>(a.M, s_nodes, me, bd, bi);
+  float w[K];
+  cn_weights<K>(a, bi, bd, w);
   const float m = a.mask ? a.mask[i] : 1.0f;
   const float x0 = me[0].x, x1 = me[0].y, x2 = me[0].z;
-  float t0 = 0.f, t1 = 0.f, t2 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float acc[10];
+#pragma unroll
+  for (int c = 0; c < 10; ++c) acc[c] = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    w[k] = w[k] / vsum;
     const int n = bi[k];
     a.nn_idx[(size_t)i * K + k] = n;
     a.nn_weight[(size_t)i * K + k] = w[k];
     a.nn_dist[(size_t)i * K + k] = bd[k];
-    float y0 = a.trans[3 * n + 0], y1 = a.trans[3 * n + 1], y2 = a.trans[3 * n + 2];
-    if (a.flags & CN_LOCAL_FRAME) {
-      const float q[4] = {a.local_rot[4 * n + 0] + 1.0f, a.local_rot[4 * n + 1], a.local_rot[4 * n + 2], a.local_rot[4 * n + 3]};
-      float R[9];
-      cn_quat_to_mat(q, R);
-      const float4 nd = s_nodes[n * DP4];
-      const float r0 = x0 - nd.x, r1 = x1 - nd.y, r2 = x2 - nd.z;
-      y0 += R[0] * r0 + R[1] * r1 + R[2] * r2 + nd.x;
-      y1 += R[3] * r0 + R[4] * r1 + R[5] * r2 + nd.y;
-      y2 += R[6] * r0 + R[7] * r1 + R[8] * r2 + nd.z;
+    cn_blend_node(a.flags, cn_load_rec(a.flags, a.trans, a.rot, a.scale, a.local_rot, n), w[k], x0, x1, x2, &s_nodes[n * DP4], acc);
+  }
+  cn_store_blend(a.flags, acc, x0, x1, x2, m, a.d_xyz + 3 * (size_t)i, a.d_rot + 4 * (size_t)i, a.d_scale + 3 * (size_t)i);
+}
+
+// Playback (inference only): the T frames of a time track over ONE cloud in one launch, one Gaussian per thread.  The scan, the
+// K-list and the weights do not depend on time (cal_nn_weight reads the canonical cloud and the node parameters only): they are
+// made once and stay in registers with the K nodes' xyz; per frame the thread gathers its K nodes' records of that frame
+// straight from the (T, M, .) tables (L2-resident) and writes one row of each frame-major output.  a.trans / a.rot / a.scale /
+// a.local_rot: (T, M, .); a.d_xyz / a.d_rot / a.d_scale: (T, N, .).
+// Stores: d_rot is one 16-byte store per row.  The 12-byte rows of d_xyz and d_scale go through a wave-private LDS tile (the
+// node table is dead once the scan is over) and leave as three unit-stride wave stores each: a wave's 64 rows are contiguous.
+#define CN_SEQ_TILE 384  // floats per wave: 64 rows x 3 of d_xyz, then of d_scale
+template <int K, int DP4>
+__global__ void __launch_bounds__(256) cnode_sequence_kernel(CNodeArgs a, int T) {
+  extern __shared__ float4 s_nodes[];
+  cn_stage_nodes<DP4>(a, s_nodes);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool on = i < a.N;
+  const int row = on ? i : a.N - 1;
+  float4 me[DP4];
+  cn_load_point<DP4>(a, row, me);
+  float bd[K];
+  int bi[K];
+  cn_select<K, DP4>(a.M, s_nodes, me, bd, bi);
+  float w[K];
+  cn_weights<K>(a, bi, bd, w);
+  const float m = a.mask ? a.mask[row] : 1.0f;
+  const float x0 = me[0].x, x1 = me[0].y, x2 = me[0].z;
+  float4 nd[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    nd[k] = s_nodes[bi[k] * DP4];
+    if (on) {
+      a.nn_idx[(size_t)i * K + k] = bi[k];
+      a.nn_weight[(size_t)i * K + k] = w[k];
+      a.nn_dist[(size_t)i * K + k] = bd[k];
     }
-    t0 += w[k] * y0; t1 += w[k] * y1; t2 += w[k] * y2;
-    const float bias = (a.flags & CN_ROT_AS_RES) ? 0.f : 1.f;
-    q0 += w[k] * (a.rot[4 * n + 0] + bias); q1 += w[k] * a.rot[4 * n + 1]; q2 += w[k] * a.rot[4 * n + 2]; q3 += w[k] * a.rot[4 * n + 3];
-    s0 += w[k] * a.scale[3 * n + 0]; s1 += w[k] * a.scale[3 * n + 1]; s2 += w[k] * a.scale[3 * n + 2];
   }
-  if (a.flags & CN_LOCAL_FRAME) { t0 -= x0; t1 -= x1; t2 -= x2; }
-  a.d_xyz[3 * (size_t)i + 0] = t0 * m; a.d_xyz[3 * (size_t)i + 1] = t1 * m; a.d_xyz[3 * (size_t)i + 2] = t2 * m;
-  if (a.flags & CN_ROT_AS_RES) {
-    a.d_rot[4 * (size_t)i + 0] = q0 * m;
-  } else {
-    a.d_rot[4 * (size_t)i + 0] = (q0 - 1.0f) * m + 1.0f;
+  __syncthreads();  // every thread has read the node table: its LDS becomes the waves' store tiles
+  const int lane = threadIdx.x & 63, wave0 = i - lane;  // the wave's first Gaussian
+  if (wave0 >= a.N) return;
+  const int valid = 3 * min(64, a.N - wave0);  // floats of the wave's rows in d_xyz / d_scale
+  float* tile = reinterpret_cast<float*>(s_nodes) + (threadIdx.x >> 6) * CN_SEQ_TILE;
+  const bool local = a.flags & CN_LOCAL_FRAME;
+  for (int f = 0; f < T; ++f) {
+    const size_t fm = (size_t)f * a.M, o = (size_t)f * a.N + wave0;
+    float acc[10];
+#pragma unroll
+    for (int c = 0; c < 10; ++c) acc[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      cn_blend_node(a.flags, cn_load_rec4(a.flags, a.trans + 3 * fm, a.rot + 4 * fm, a.scale + 3 * fm, local ? a.local_rot + 4 * fm : nullptr, bi[k]),
+                    w[k], x0, x1, x2, &nd[k], acc);
+    float q[4];
+    cn_store_blend(a.flags, acc, x0, x1, x2, m, tile + 3 * lane, q, tile + 192 + 3 * lane);
+    if (on) reinterpret_cast<float4*>(a.d_rot)[o + lane] = make_float4(q[0], q[1], q[2], q[3]);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int e = 64 * j + lane;
+      if (e < valid) { a.d_xyz[3 * o + e] = tile[e]; a.d_scale[3 * o + e] = tile[192 + e]; }
+    }
+    __builtin_amdgcn_wave_barrier();  // (the tile is read before the next frame writes it)
   }
-  a.d_rot[4 * (size_t)i + 1] = q1 * m; a.d_rot[4 * (size_t)i + 2] = q2 * m; a.d_rot[4 * (size_t)i + 3] = q3 * m;
-  a.d_scale[3 * (size_t)i + 0] = s0 * m; a.d_scale[3 * (size_t)i + 1] = s1 * m; a.d_scale[3 * (size_t)i + 2] = s2 * m;
 }
 
 // accumulator columns of a node: [0:3] translation, [3:7] rotation, [7:10] scale, [10:19] dL/dR (row-major), [19] radius,
@@ -426,6 +556,17 @@ static void cn_launch_forward(const CNodeArgs& a, int dp4, hipStream_t s) {
   }
 }
 
+template <int K>
+static void cn_launch_sequence(const CNodeArgs& a, int T, int dp4, size_t lds, hipStream_t s) {
+  const dim3 grid((a.N + 255) / 256), block(256);
+  switch (dp4) {
+    case 1: hipLaunchKernelGGL((cnode_sequence_kernel<K, 1>), grid, block, lds, s, a, T); break;
+    case 2: hipLaunchKernelGGL((cnode_sequence_kernel<K, 2>), grid, block, lds, s, a, T); break;
+    case 3: hipLaunchKernelGGL((cnode_sequence_kernel<K, 3>), grid, block, lds, s, a, T); break;
+    default: hipLaunchKernelGGL((cnode_sequence_kernel<K, 4>), grid, block, lds, s, a, T); break;
+  }
+}
+
 }  // namespace riggs
 
 using namespace riggs;
@@ -475,6 +616,43 @@ int riggs_cnode_forward(int32_t N, int32_t M, int32_t K, int32_t hyper, int32_t 
     case 7: cn_launch_forward<7>(a, dp4, s); break;
     default: cn_launch_forward<8>(a, dp4, s); break;
   }
+  RIGGS_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// the kernel has no passes: a frame's records are gathered straight from the (T, M, .) tables
+int32_t riggs_cnode_sequence_pass_frames(int32_t M, int32_t flags) { return 1; }
+
+int riggs_cnode_sequence_forward(int32_t N, int32_t M, int32_t T, int32_t K, int32_t hyper, int32_t feat_stride, int32_t node_stride,
+                                 int32_t flags, const float* x, const float* feature, const float* motion_mask, const float* nodes,
+                                 const float* node_radius_log, const float* node_weight_logit, const float* node_trans,
+                                 const float* node_rot, const float* node_scale, const float* local_rot, float* d_xyz, float* d_rot,
+                                 float* d_scale, int32_t* nn_idx, float* nn_weight, float* nn_dist, riggs_stream stream) {
+  if (int rc = cn_check(N, M, K, hyper, feat_stride, node_stride, feature)) return rc;
+  RIGGS_REQUIRE(T >= 0, "bad sizes");
+  RIGGS_REQUIRE(!(flags & CN_LOCAL_FRAME) || local_rot || T == 0, "local_frame needs local_rotation");
+  if (N == 0 || T == 0) return 0;
+  RIGGS_REQUIRE(x && nodes && node_radius_log && node_trans && node_rot && node_scale && d_xyz && d_rot && d_scale && nn_idx &&
+                nn_weight && nn_dist, "NULL buffer");
+  RIGGS_REQUIRE((((uintptr_t)node_rot | (uintptr_t)local_rot | (uintptr_t)d_rot) & 15) == 0,
+                "node_rot, local_rot and d_rot must be 16-byte aligned");
+  RIGGS_REQUIRE((long long)T * M <= 0x7fffffffLL / 4, "track too long: split it into chunks");
+  const int dp4 = (3 + hyper + 3) / 4;
+  RIGGS_REQUIRE((size_t)M * dp4 * 16 <= 128 * 1024, "control nodes do not fit the 128 KB LDS table");
+  size_t lds = (size_t)M * dp4 * 16;
+  if (lds < 4 * CN_SEQ_TILE * sizeof(float)) lds = 4 * CN_SEQ_TILE * sizeof(float);  // the four waves' store tiles
+  CNodeArgs a = cn_args(N, M, K, hyper, feat_stride, node_stride, flags, x, feature, motion_mask, nodes, node_radius_log,
+                        node_weight_logit, node_trans, node_rot, node_scale, local_rot);
+  a.d_xyz = d_xyz; a.d_rot = d_rot; a.d_scale = d_scale; a.nn_idx = nn_idx; a.nn_weight = nn_weight; a.nn_dist = nn_dist;
+  hipStream_t s = (hipStream_t)stream;
+  static unsigned long long attr_set = 0ull;
+  if (once_per_device(attr_set)) {
+#define CN_SATTR(KK, DD) RIGGS_HIP_CHECK(hipFuncSetAttribute((const void*)cnode_sequence_kernel<KK, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+#define CN_SATTR4(KK) CN_SATTR(KK, 1) CN_SATTR(KK, 2) CN_SATTR(KK, 3) CN_SATTR(KK, 4)
+    CN_SATTR4(1) CN_SATTR4(2) CN_SATTR4(3) CN_SATTR4(4) CN_SATTR4(5) CN_SATTR4(6) CN_SATTR4(7) CN_SATTR4(8)
+  }
+#define CN_SLAUNCH(KK) case KK: cn_launch_sequence<KK>(a, T, dp4, lds, s); break;
+  switch (K) { CN_SLAUNCH(1) CN_SLAUNCH(2) CN_SLAUNCH(3) CN_SLAUNCH(4) CN_SLAUNCH(5) CN_SLAUNCH(6) CN_SLAUNCH(7) CN_SLAUNCH(8) }
   RIGGS_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -19,7 +19,7 @@ from . import _lib as L
 from .skeleton import _mask_tensor, _zero_scaling
 
 __all__ = ["slerp_batch", "run_interpolation", "get_geometric_color", "get_color_for_skinning_weights", "skinning_colors",
-           "deform_sequence", "render_sequence", "sequence_pass_frames"]
+           "deform_sequence", "render_sequence", "sequence_pass_frames", "render_time_sequence"]
 
 
 # --------------------------------------------------------------------------- key poses -> a pose track
@@ -226,3 +226,37 @@ def render_sequence(viewpoint_camera, pc, sw, pipe, bg_color, poses, motion_mask
             pkg = render(*args, d_rot_as_res=d_rot_as_res, keep_lists=bool(skinning))
             skin = render(*args, d_rot_as_res=d_rot_as_res, override_color=colours, lists=pkg.lists) if skinning else None
             yield pkg, skin, seq["d_nodes"][f]
+
+
+# --------------------------------------------------------------------------- stage 1: a time track over one cloud
+def render_time_sequence(viewpoint_camera, pc, warp, pipe, bg_color, times, chunk=32):
+    """Stage-1 playback (the reference's render.py modes ``render_set`` / ``interpolate_time`` / ``interpolate_all``,
+    render.py:100-116, :157-235): a generator over ``times`` (T,) that yields ``(pkg, d_nodes[f])`` per time, where ``pkg`` is
+    ``render(camera, pc, pipe, bg_color, d_xyz[f], d_rotation[f], d_scaling[f], d_opacity=, d_color=, d_rot_as_res=warp.d_rot_as_res)``
+    on the frames of ``ControlNodeWarp.deform_sequence``: ``chunk`` times per call, which bounds the (chunk, N, 10) buffers; the
+    scan of the control nodes runs once per chunk, not once per frame.  ``viewpoint_camera``: one camera, or a list of one per
+    time (``interpolate_all`` moves the camera with the time).  ``warp``: a ``ControlNodeWarp`` or a model holding one as
+    ``.deform``.  With ``pc.use_isotropic_gs`` the rotation and scale residuals are zeroed (render.py:112-114).  Inference only."""
+    from .render import render
+    warp = getattr(warp, "deform", warp)
+    x = pc.get_xyz.detach()
+    times = torch.as_tensor(times, dtype=torch.float32, device=x.device)
+    if times.dim() != 1:
+        raise ValueError("render_time_sequence: times must be (T,), got %s" % (tuple(times.shape),))
+    T = int(times.shape[0])
+    cams = list(viewpoint_camera) if isinstance(viewpoint_camera, (list, tuple)) else None
+    if cams is not None and len(cams) != T:
+        raise ValueError("render_time_sequence: %d cameras for %d times" % (len(cams), T))
+    chunk = max(1, int(chunk))
+    iso = bool(getattr(pc, "use_isotropic_gs", False))
+    for c0 in range(0, T, chunk):
+        seq = warp.deform_sequence(x, times[c0:c0 + chunk], pc.feature, pc.motion_mask)
+        if iso:
+            seq["d_rotation"], seq["d_scaling"] = torch.zeros_like(seq["d_rotation"]), torch.zeros_like(seq["d_scaling"])
+        at = lambda k, f: None if seq[k] is None else seq[k][f]  # noqa: E731
+        for f in range(seq["d_xyz"].shape[0]):
+            cam = viewpoint_camera if cams is None else cams[c0 + f]
+            with torch.no_grad():
+                pkg = render(cam, pc, pipe, bg_color, seq["d_xyz"][f], seq["d_rotation"][f], seq["d_scaling"][f],
+                             d_opacity=at("d_opacity", f), d_color=at("d_color", f), d_rot_as_res=warp.d_rot_as_res)
+            yield pkg, seq["d_nodes"][f]

@@ -491,7 +491,7 @@ def load_skeleton_tree(path, device="cpu"):
 # ---- train_rig.py:192-262 and the tail of init_skeleton_info (:135-141) --------------------------------------------------
 @torch.no_grad()
 def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=None, num_gs_sample=0, manually_key_frame=-1,
-                            cameras=None, symmetry=False):
+                            cameras=None, symmetry=False, sequence_chunk=None):
     """The trained stage 1 at every training frame, and the skeleton drawn from it.  ``deform``: a ``ControlNodeWarp`` (or a
     model holding one as ``.deform``); ``gaussians``: the stage-1 ``GaussianModel``; ``fids`` (F,): the training frames' times,
     visited in ascending order (``coverage`` (F,), the frames' mask areas, is given in the order of ``fids``).
@@ -508,7 +508,11 @@ def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=N
     the frames of the labels the nodes project onto, ``node_semantic_labels(d_nodes, cameras)[1]``, and ``nodes_semantic_label``
     (F, M) is returned in the first dict; without cameras an all-zero vector, what the reference passes for a dataset without
     semantic maps (which still pairs chains, by length alone).  The default ``symmetry=False`` passes None — no symmetry pass,
-    which the reference's trainer never does; ``cameras`` alone changes nothing."""
+    which the reference's trainer never does; ``cameras`` alone changes nothing.
+
+    ``sequence_chunk=None``: one ``forward`` per frame, as the reference.  An integer: the frames go through
+    ``ControlNodeWarp.deform_sequence`` in chunks of that size — the scan of the control nodes once per chunk instead of once
+    per frame; the results agree with the loop's to float32 rounding."""
     from .skeleton import write_to_obj
     warp = getattr(deform, "deform", deform)
     if num_gs_sample > 10:
@@ -526,11 +530,18 @@ def precompute_deformations(deform, gaussians, fids, coverage=None, model_path=N
         cameras = [cameras[int(i)] for i in order]
     xyz = gaussians.get_xyz.detach()
     stacks = {"d_xyz": [], "d_nodes": [], "d_rotation": [], "d_scaling": []}
-    for i in range(fids.shape[0]):
-        d = warp(xyz, warp.expand_time(fids[i:i + 1]), feature=gaussians.feature, motion_mask=gaussians.motion_mask)
-        for k in stacks:
-            stacks[k].append(d[k].detach())
-    info = {k: torch.stack(v) for k, v in stacks.items()}
+    if sequence_chunk is None:
+        for i in range(fids.shape[0]):
+            d = warp(xyz, warp.expand_time(fids[i:i + 1]), feature=gaussians.feature, motion_mask=gaussians.motion_mask)
+            for k in stacks:
+                stacks[k].append(d[k].detach())
+        info = {k: torch.stack(v) for k, v in stacks.items()}
+    else:
+        for c0 in range(0, fids.shape[0], max(1, int(sequence_chunk))):
+            d = warp.deform_sequence(xyz, fids[c0:c0 + max(1, int(sequence_chunk))], gaussians.feature, gaussians.motion_mask)
+            for k in stacks:
+                stacks[k].append(d[k])
+        info = {k: torch.cat(v) for k, v in stacks.items()}
     template_idx = select_key_frame(info["d_nodes"], coverage, manually_key_frame)
     seg_labels = None
     if symmetry and cameras is not None:
