@@ -43,9 +43,11 @@ def quat_R(q):
 
 
 def render(means3D, means2D, opac, view, proj, campos, tanx, tany, H, W, bg, shs=None, colors=None, scales=None,
-           rots=None, cov6=None, deg=3, mod=1.0):
+           rots=None, cov6=None, deg=3, mod=1.0, taps=None):
     """All tensor inputs float64.  view/proj are the transposed (row-vector) 4x4 matrices.
-    Returns color (3,H,W), depth (H,W), alpha (H,W), radii (N), n_contrib (H,W)."""
+    Returns color (3,H,W), depth (H,W), alpha (H,W), radii (N), n_contrib (H,W).
+    ``taps``: a dict that receives the per-Gaussian tensors the compositing reads (ndc, conic A / B / C, rgb, and the depth it
+    blends: a copy of t_z, so that its gradient is the compositing's alone), for tests that split the chain there."""
     N = means3D.shape[0]
     dt = means3D.dtype
     ones = torch.ones(N, 1, dtype=dt)
@@ -95,6 +97,9 @@ def render(means3D, means2D, opac, view, proj, campos, tanx, tany, H, W, bg, shs
         rgb = torch.clamp_min(eval_sh(deg, shs, d) + 0.5, 0.0)
     else:
         rgb = colors
+    tzd = tz * 1.0
+    if taps is not None:
+        taps.update(ndc=ndc, A=A_, B=B_, C=C_, rgb=rgb, depth=tzd, opacity=opac)
     order = torch.argsort(tz.detach().float(), stable=True)  # fp32 depth bits decide the order
     ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
     tyi, txi = torch.div(ys, 16, rounding_mode="floor"), torch.div(xs, 16, rounding_mode="floor")
@@ -124,7 +129,7 @@ def render(means3D, means2D, opac, view, proj, campos, tanx, tany, H, W, bg, shs
         use = ok & ~stop
         w = torch.where(use, alpha * T, torch.zeros_like(T))
         col = col + rgb[k][:, None, None] * w
-        dep = dep + tz[k] * w
+        dep = dep + tzd[k] * w
         alp = alp + w
         T = torch.where(use, testT, T)
         ncontrib = torch.where(use, count, ncontrib)
