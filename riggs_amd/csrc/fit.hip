@@ -20,7 +20,8 @@
 //   4  cg_steps steps of PCG from x = 0 on A x = b; before a step: stop unless r.z > FIT_CG_EPS * (r.z at the start); stop
 //      unless p.Ap > 0.  The updates behind the last step's x are not computed.
 //   5  IK's step 5 with omega_a = x_a; global_trans += extent x_tau'
-// and one more FK behind the last iteration for d_nodes and the residual.
+// and one more FK behind the last iteration for d_nodes and the residual.  The inputs, the FK and the clamped step of 1, 5 and the
+// result are the frame this solver shares with ik.hip: pose_solve.h has them, here are the operators, 3 and 4.
 //
 // ONE workgroup per problem, ALL iterations in one launch; thread j owns joint j and keeps q, x, r, p, z and Minv in registers;
 // every thread carries the three tau' components (the same values).  J <= 64: one wave64, the sweeps by lane shuffles
@@ -31,26 +32,23 @@
 // wave order and the tau' term last: one LDS round trip, two slots in turn.  No float atomics: the same inputs give the same
 // bits, and a problem never reads its neighbours.  What bounds it is the chain of dependent steps (levels x 2 sweeps x cg_steps
 // x iterations), not bytes.
-#include "fk_device.h"
-
-#include <type_traits>
+#include "pose_solve.h"
 
 namespace riggs {
 
 #define FIT_CG_EPS 1e-10f  // (include/riggs_hip.h states it; tests/fit_ref.py: CG_EPS)
 
 struct FitArgs {
-  int J, iterations, cg_steps, relative, solve_translation;
-  float damping, max_step;
-  const float* joints; const int32_t* parents; const float* local_rot_in; const float* global_trans_in;
-  const float* targets; const float* weights; const uint8_t* locked; const float* extent;
-  float* local_rot_out; float* global_trans_out; float* d_nodes; float* residual;
+  SolveArgs s;
+  int cg_steps;
+  const float* targets; const float* weights;
 };
 
-struct FitWideShared {
-  FkWideShared fk;              // fk.A is the up-sweeps' row buffer
-  float dn[MAX_J_WIDE][8];      // the down-sweeps' row buffer
-  float part[2][8];             // a dot product's slot: the four waves' sums, then the root's four values
+template <bool WIDE>
+struct FitShared {  // (one wave sweeps and sums by lane shuffles: it touches none of this, and no LDS is set aside for it)
+  typename SolveChain<WIDE>::Shared fk;  // fk.A is the up-sweeps' row buffer
+  float dn[WIDE ? MAX_J_WIDE : 1][8];    // the down-sweeps' row buffer
+  float part[2][8];                      // a dot product's slot: the four waves' sums, then the root's four values
 };
 
 __device__ __forceinline__ float dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -61,8 +59,8 @@ __device__ __forceinline__ void cross3(const float (&a)[3], const float (&b)[3],
 }
 
 // The workgroup's sum of `term`, the same bits in every thread; root[0..3] of thread 0 reaches every thread on the same trip.
-template <bool WIDE, typename WS>
-__device__ __forceinline__ float fit_dot(float term, float (&root)[4], WS& ws, int& slot) {
+template <bool WIDE>
+__device__ __forceinline__ float fit_dot(float term, float (&root)[4], FitShared<WIDE>& ws, int& slot) {
   if constexpr (WIDE) {
     const int j = threadIdx.x;
     const float v = wave_sum(term);
@@ -88,26 +86,19 @@ template <bool WIDE>
 __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
   constexpr int NJ = WIDE ? MAX_J_WIDE : MAX_J;
   __shared__ float pos[NJ][3];  // posed joints of this iteration
-  __shared__ typename std::conditional<WIDE, FitWideShared, int>::type wsh;
-  typedef typename std::conditional<WIDE, FkWide, FkLane>::type Fk;
+  __shared__ FitShared<WIDE> wsh;
   const int b = blockIdx.x, j = threadIdx.x;
-  const int J = a.J;
+  const int J = a.s.J;
   const bool on = j < J;
 
-  // ---- the problem's inputs.  A parent outside [0, j) is clamped into it: no index leaves the arrays.
-  FkIn in = {};
-  in.q[0] = 1.f;
-  bool locked = false, live = false;
+  // ---- the problem's inputs (pose_solve.h), then the joint's target
+  const float ext = a.s.extent[0];
+  SolveIn pr;
+  float gt[3];
+  solve_load(a.s, b, j, ext, pr, gt);
+  bool live = false;
   float s = 0.f, tg[3] = {0.f, 0.f, 0.f};
   if (on) {
-    int vp = 0;
-    if (j >= 1) vp = min(max(a.parents[j], 0), j - 1);
-    in.par = vp;
-#pragma unroll
-    for (int e = 0; e < 4; e++) in.q[e] = a.local_rot_in[((size_t)b * J + j) * 4 + e];
-#pragma unroll
-    for (int e = 0; e < 3; e++) { in.x[e] = a.joints[3 * j + e]; in.c[e] = a.joints[3 * vp + e]; }
-    locked = a.locked && a.locked[j] != 0;
     const float w = a.weights ? a.weights[(size_t)b * J + j] : 1.f;
     live = w > 0.f;  // (a NaN weight: off)
     if (live) {      // a target without weight is not read at all
@@ -116,60 +107,29 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
       for (int c = 0; c < 3; c++) tg[c] = a.targets[((size_t)b * J + j) * 3 + c];
     }
   }
-  const bool turn = on && !locked;
-  float gt[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) gt[c] = a.global_trans_in[(size_t)b * 3 + c];
-  const float ext = a.extent[0];
-  const float damping = (a.relative & 1) ? a.damping * ext : a.damping;
-  const float max_step = (a.relative & 2) ? a.max_step * ext : a.max_step;
-  const float damping2 = damping * damping;
-  const bool trans = a.solve_translation != 0;
+  const bool turn = on && !pr.locked;
+  const float damping2 = pr.damping2;
+  const bool trans = a.s.solve_translation != 0;
   int slot = 0;
 
   // ---- topology and the first sweep
-  Fk f;
-  if constexpr (WIDE) fk_block_forward(J, in, f, wsh.fk);
-  else fk_wave_forward(J, in, f);
+  typedef SolveChain<WIDE> Chain;
+  typename Chain::Fk f;
+  Chain::forward(J, pr.in, f, wsh.fk);
 
   for (int it = 0;; it++) {
-    if (it > 0) {
-      if constexpr (WIDE) fk_block_sweep(J, in, f, wsh.fk);
-      else fk_wave_sweep(J, in, f);
-    }
-    float G[12];
-#pragma unroll
-    for (int e = 0; e < 12; e++) {
-      if constexpr (WIDE) G[e] = wsh.fk.G[j][e];
-      else G[e] = f.G[e];
-    }
-    if (on) {
-#pragma unroll
-      for (int r = 0; r < 3; r++)  // (fk_forward_kernel's d_nodes, operation for operation)
-        pos[j][r] = (G[4 * r] * in.x[0] + G[4 * r + 1] * in.x[1] + G[4 * r + 2] * in.x[2] + G[4 * r + 3]) + gt[r];
-    }
+    if (it > 0) Chain::sweep(J, pr.in, f, wsh.fk);
+    Chain::posed(f, wsh.fk, pr, gt, on, pos[j]);
     __syncthreads();
-    if (it >= a.iterations) break;
+    if (it >= a.s.iterations) break;
 
     // ---- 1: positions about the posed root, the clamped weighted step
     float pc[3] = {0.f, 0.f, 0.f}, pv[3] = {0.f, 0.f, 0.f}, rr[3] = {0.f, 0.f, 0.f};
     if (on) {
 #pragma unroll
-      for (int c = 0; c < 3; c++) { pc[c] = pos[j][c] - pos[0][c]; pv[c] = pos[in.par][c] - pos[0][c]; }
+      for (int c = 0; c < 3; c++) { pc[c] = pos[j][c] - pos[0][c]; pv[c] = pos[pr.in.par][c] - pos[0][c]; }
     }
-    if (live) {
-      float d[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) d[c] = tg[c] - pos[j][c];
-      const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      if (len > max_step) {
-        const float k = max_step / len;
-#pragma unroll
-        for (int c = 0; c < 3; c++) d[c] = d[c] * k;
-      }
-#pragma unroll
-      for (int c = 0; c < 3; c++) rr[c] = s * d[c];
-    }
+    if (live) clamped_step(tg, pos[j], pr.max_step, s, rr);
     // ---- 3 (and b = J^T r): one up-sweep of F, M, S0, S1, S2
     float bq[3], minv;
     float root[4];
@@ -183,8 +143,8 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
       for (int c = 0; c < 3; c++) { v[c] = fh[c]; v[3 + c] = mh[c]; v[7 + c] = s2 * pc[c]; }
       v[6] = s2;
       v[10] = s2 * dot3(pc, pc);
-      if constexpr (WIDE) fk_block_subtree(J, f, wsh.fk, wsh.fk.A, v);
-      else fk_wave_subtree(J, f, v);
+      if constexpr (WIDE) fk_block_subtree(J, f, wsh.fk, wsh.fk.A, v);  // (written out in both forms, here and twice below:
+      else fk_wave_subtree(J, f, v);                                    // through a wrapper this kernel is 13 % slower, pose_solve.h)
       const float F[3] = {v[0], v[1], v[2]}, S1[3] = {v[7], v[8], v[9]};
       float pf[3];
       cross3(pv, F, pf);
@@ -198,7 +158,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
     float x[3] = {0.f, 0.f, 0.f}, r[3], z[3], p[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) { r[c] = bq[c]; z[c] = minv * r[c]; p[c] = z[c]; }
-    float rz = fit_dot<WIDE>(dot3(r, z), root, wsh, slot);
+    float rz = fit_dot(dot3(r, z), root, wsh, slot);
     float xt[3] = {0.f, 0.f, 0.f}, rt[3] = {0.f, 0.f, 0.f}, zt[3] = {0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f}, minvt = 0.f;
     if (trans) {
       minvt = 1.f / ((ext * ext) * root[3] + damping2);
@@ -242,7 +202,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
         for (int c = 0; c < 3; c++) Ap[c] = turn ? (v[3 + c] - pf[c]) + damping2 * p[c] : 0.f;
         root[0] = v[0]; root[1] = v[1]; root[2] = v[2]; root[3] = 0.f;
       }
-      float pAp = fit_dot<WIDE>(dot3(p, Ap), root, wsh, slot);
+      float pAp = fit_dot(dot3(p, Ap), root, wsh, slot);
       if (trans) {
 #pragma unroll
         for (int c = 0; c < 3; c++) Apt[c] = ext * root[c] + damping2 * pt[c];
@@ -258,54 +218,20 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void fit_pose_kernel(FitArgs a) {
         r[c] = r[c] - alpha * Ap[c]; z[c] = minv * r[c];
         rt[c] = rt[c] - alpha * Apt[c]; zt[c] = minvt * rt[c];
       }
-      const float rzn = fit_dot<WIDE>(dot3(r, z), root, wsh, slot) + dot3(rt, zt);
+      const float rzn = fit_dot(dot3(r, z), root, wsh, slot) + dot3(rt, zt);
       const float beta = rzn / rz;
 #pragma unroll
       for (int c = 0; c < 3; c++) { p[c] = z[c] + beta * p[c]; pt[c] = zt[c] + beta * pt[c]; }
       rz = rzn;
     }
     // ---- 5: omega_a = x_a into the parent's frame, onto the quaternion
-    float Rp[9];  // the parent's rotation (the lane shuffles are taken by every lane)
-#pragma unroll
-    for (int r9 = 0; r9 < 3; r9++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        if constexpr (WIDE) Rp[3 * r9 + c] = wsh.fk.G[in.par][4 * r9 + c];
-        else Rp[3 * r9 + c] = fk_lane_get(f.G[4 * r9 + c], in.par);
-      }
-    float dl[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) dl[c] = (j == 0) ? x[c] : Rp[c] * x[0] + Rp[3 + c] * x[1] + Rp[6 + c] * x[2];
-    const float th = sqrtf(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
-    if (turn && th > 0.f) {
-      const float half = 0.5f * th, k = sinf(half) / th;
-      const float aw = cosf(half), ax = k * dl[0], ay = k * dl[1], az = k * dl[2];
-      const float bw = in.q[0], bx = in.q[1], by = in.q[2], bz = in.q[3];
-      in.q[0] = aw * bw - ax * bx - ay * by - az * bz;
-      in.q[1] = aw * bx + ax * bw + ay * bz - az * by;
-      in.q[2] = aw * by - ax * bz + ay * bw + az * bx;
-      in.q[3] = aw * bz + ax * by - ay * bx + az * bw;
-    }
-    if (trans) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) gt[c] = gt[c] + ext * xt[c];
-    }
+    const float dgt[3] = {ext * xt[0], ext * xt[1], ext * xt[2]};
+    Chain::turn(f, wsh.fk, x, turn, trans, dgt, pr, gt);
   }
 
-  // ---- the result (pos is the posed skeleton of the final quaternions, behind a barrier)
-  if (on) {
-#pragma unroll
-    for (int e = 0; e < 4; e++) a.local_rot_out[((size_t)b * J + j) * 4 + e] = in.q[e];
-#pragma unroll
-    for (int c = 0; c < 3; c++) a.d_nodes[((size_t)b * J + j) * 3 + c] = pos[j][c];
-    float res = 0.f;
-    if (live) {
-      const float d0 = tg[0] - pos[j][0], d1 = tg[1] - pos[j][1], d2 = tg[2] - pos[j][2];
-      res = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-    }
-    a.residual[(size_t)b * J + j] = res;
-  }
-  if (j < 3) a.global_trans_out[(size_t)b * 3 + j] = gt[j];
+  // ---- the result (pos is the posed skeleton of the final quaternions, behind a barrier); a joint without weight: 0
+  solve_write(a.s, b, j, pr, gt, pos);
+  if (on) a.s.residual[(size_t)b * J + j] = live ? solve_distance(tg, pos[j]) : 0.f;
 }
 
 }  // namespace riggs
@@ -319,19 +245,12 @@ int riggs_fit_pose(int32_t B, int32_t J, const float* joints, const int32_t* par
                    int32_t iterations, int32_t cg_steps, float damping, float max_step, const float* extent, int32_t relative,
                    int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
                    riggs_stream stream) {
-  RIGGS_REQUIRE(B >= 1, "riggs_fit_pose: needs B >= 1");
-  RIGGS_REQUIRE(J >= 1 && J <= MAX_J_WIDE, "riggs_fit_pose: num_joints must be in [1, 256]");
-  RIGGS_REQUIRE(iterations >= 0 && cg_steps >= 1, "riggs_fit_pose: iterations >= 0 and cg_steps >= 1");
-  RIGGS_REQUIRE((relative & ~3) == 0, "riggs_fit_pose: relative is a mask of bits 0 and 1");
-  RIGGS_REQUIRE(damping > 0.f && max_step >= 0.f, "riggs_fit_pose: needs damping > 0 and max_step >= 0");  // (a NaN fails both)
-  RIGGS_REQUIRE(joints && parents && local_rot_in && global_trans_in && targets && extent && local_rot_out && global_trans_out &&
-                    d_nodes && residual, "riggs_fit_pose: NULL argument (extent is always needed: it scales the translation unknown)");
   FitArgs a;
-  a.J = J; a.iterations = iterations; a.cg_steps = cg_steps; a.relative = relative; a.solve_translation = solve_translation != 0;
-  a.damping = damping; a.max_step = max_step;
-  a.joints = joints; a.parents = parents; a.local_rot_in = local_rot_in; a.global_trans_in = global_trans_in;
-  a.targets = targets; a.weights = weights; a.locked = locked; a.extent = extent;
-  a.local_rot_out = local_rot_out; a.global_trans_out = global_trans_out; a.d_nodes = d_nodes; a.residual = residual;
+  if (int rc = solve_args("riggs_fit_pose", B, J, joints, parents, local_rot_in, global_trans_in, locked, iterations, damping, max_step,
+                          extent, relative, solve_translation, local_rot_out, global_trans_out, d_nodes, residual, a.s)) return rc;
+  RIGGS_REQUIRE(cg_steps >= 1, "riggs_fit_pose: cg_steps >= 1");
+  RIGGS_REQUIRE(targets && extent, "riggs_fit_pose: NULL argument (extent is always needed: it scales the translation unknown)");
+  a.cg_steps = cg_steps; a.targets = targets; a.weights = weights;
   if (J <= MAX_J) hipLaunchKernelGGL(fit_pose_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(fit_pose_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
   RIGGS_HIP_CHECK(hipGetLastError());

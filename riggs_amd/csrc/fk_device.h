@@ -398,136 +398,4 @@ __device__ __forceinline__ void fk_block_backward(int J, const FkIn& in, const F
   fk_dq_from_dT(on, in, dT, dq);
 }
 
-// ---- the level sweep alone, for a caller that changes the rotations and runs the chain again (ik.hip: once per iteration).
-// `f` (and `sh`) come from an earlier fk_wave_forward / fk_block_forward over the same parents, whose topology — levels,
-// children, the deepest level — is kept; the local transforms are renewed from in.q and the sweep G_i = G_parent(i) T_i is the
-// forward's, operation for operation.  Call with all lanes (threads) of the wave (workgroup).
-__device__ __forceinline__ void fk_wave_sweep(int J, const FkIn& in, FkLane& f) {
-  const int j = threadIdx.x & 63;
-  if (j < J) fk_local_T(in, f.T);
-#pragma unroll
-  for (int e = 0; e < 12; e++) f.G[e] = f.T[e];
-  for (int l = 1; l <= f.maxlev; l++) {
-    float Gp[12];
-#pragma unroll
-    for (int e = 0; e < 12; e++) Gp[e] = fk_lane_get(f.G[e], f.par);
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        float v = Gp[4 * r] * f.T[c] + Gp[4 * r + 1] * f.T[4 + c] + Gp[4 * r + 2] * f.T[8 + c];
-        if (c == 3) v += Gp[4 * r + 3];
-        if (j >= 1) f.G[4 * r + c] = v;
-      }
-  }
-}
-
-// ... over the block: sh.G is rewritten (behind a barrier: the previous sweep's readers are done) and final behind the last one.
-__device__ __forceinline__ void fk_block_sweep(int J, const FkIn& in, FkWide& f, FkWideShared& sh) {
-  const int j = threadIdx.x;
-  const bool on = j < J;
-  if (on) fk_local_T(in, f.T);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 12; e++) sh.G[j][e] = f.T[e];
-  __syncthreads();
-  for (int l = 1; l <= f.maxlev; l++) {
-    if (on && f.lev == l) {
-      float Gp[12];
-#pragma unroll
-      for (int e = 0; e < 12; e++) Gp[e] = sh.G[f.par][e];
-      float G[12];
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          float v = Gp[4 * r] * f.T[c] + Gp[4 * r + 1] * f.T[4 + c] + Gp[4 * r + 2] * f.T[8 + c];
-          if (c == 3) v += Gp[4 * r + 3];
-          G[4 * r + c] = v;
-        }
-#pragma unroll
-      for (int e = 0; e < 12; e++) sh.G[j][e] = G[e];
-    }
-    __syncthreads();
-  }
-}
-
-// ---- sums over the tree, for a caller whose operator is a sum along root-to-joint paths and its transpose a sum over subtrees
-// (fit.hip: the Jacobian of the chain and its transpose).  They run on the topology an earlier fk_wave_forward / fk_block_forward
-// left in `f` (`sh`): the same levels, the same children, the same order.  Call with all lanes (threads) of the wave (workgroup).
-// fk_*_prefix:  v_j <- v_vp(j) + v_j level by level from the root: v_j becomes the sum over the path root .. j.
-// fk_*_subtree: v_a <- v_a + the finished sums of a's children in descending child index, deepest level first (the order of the
-// sequential sweep i = J - 1 .. 1 and of fk_*_backward): v_a becomes the sum over a's subtree, a included.
-template <int N>
-__device__ __forceinline__ void fk_wave_prefix(const FkLane& f, float (&v)[N]) {
-  for (int l = 1; l <= f.maxlev; l++) {
-#pragma unroll
-    for (int e = 0; e < N; e++) {
-      const float t = fk_lane_get(v[e], f.par);
-      if (f.lev == l) v[e] = t + v[e];
-    }
-  }
-}
-template <int N>
-__device__ __forceinline__ void fk_wave_subtree(int J, const FkLane& f, float (&v)[N]) {
-  const int j = threadIdx.x & 63;
-  for (int l = f.maxlev - 1; l >= 0; l--) {
-    unsigned long long km = (j < J && f.lev == l) ? f.kids : 0ull;
-    while (__builtin_amdgcn_ballot_w64(km != 0ull) != 0ull) {
-      const bool has = km != 0ull;
-      const int i = has ? 63 - __builtin_clzll(km) : j;  // descending child index
-#pragma unroll
-      for (int e = 0; e < N; e++) {
-        const float t = fk_lane_get(v[e], i);
-        if (has) v[e] += t;
-      }
-      if (has) km &= ~(1ull << i);
-    }
-  }
-}
-// ... over the block, through `buf` (MAX_J_WIDE rows of at least N floats in LDS): ONE barrier per level.  The first write of a
-// call lands behind the last read of the call before it only if a barrier lies between the two calls: the caller's business
-// (fit.hip: a dot product's reduction, or the other sweep, always does).  fk_block_prefix leaves every row of `buf` final behind
-// its last barrier; rows >= J hold what their threads passed in.
-template <int N, int S>
-__device__ __forceinline__ void fk_block_prefix(int J, const FkWide& f, float (*buf)[S], float (&v)[N]) {
-  static_assert(N <= S, "fk_block_prefix: the row is too short");
-  const int j = threadIdx.x;
-#pragma unroll
-  for (int e = 0; e < N; e++) buf[j][e] = v[e];
-  __syncthreads();
-  for (int l = 1; l <= f.maxlev; l++) {
-    if (j < J && f.lev == l) {
-#pragma unroll
-      for (int e = 0; e < N; e++) { v[e] = buf[f.par][e] + v[e]; buf[j][e] = v[e]; }
-    }
-    __syncthreads();
-  }
-}
-template <int N, int S>
-__device__ __forceinline__ void fk_block_subtree(int J, const FkWide& f, const FkWideShared& sh, float (*buf)[S], float (&v)[N]) {
-  static_assert(N <= S, "fk_block_subtree: the row is too short");
-  const int j = threadIdx.x;
-  const bool on = j < J;
-  for (int l = f.maxlev - 1; l >= 0; l--) {
-    if (on && f.lev == l + 1) {
-#pragma unroll
-      for (int e = 0; e < N; e++) buf[j][e] = v[e];
-    }
-    __syncthreads();
-    if (on && f.lev == l) {
-      for (int w = FK_WIDE_WORDS - 1; w >= 0; w--) {
-        uint32_t km = sh.kids[j][w];
-        while (km != 0u) {
-          const int b = 31 - __builtin_clz(km);  // descending child index
-          const int i = 32 * w + b;
-#pragma unroll
-          for (int e = 0; e < N; e++) v[e] += buf[i][e];
-          km &= ~(1u << b);
-        }
-      }
-    }
-  }
-}
-
 }  // namespace riggs

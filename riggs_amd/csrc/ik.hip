@@ -11,7 +11,8 @@
 //      solve_translation a further block s I
 //   4  A = J J^T + damping^2 I (3E x 3E), A y = r by Cholesky; omega_a = J_{.,a}^T y, dgt = sum_e s y_e
 //   5  delta_a = R(G_vp(a))^T omega_a (the root: omega_0), theta = |delta_a|; theta > 0: q_a <- (cos theta/2, sin(theta/2) delta_a / theta) (x) q_a
-// and one more FK behind the last iteration for d_nodes and the residual.
+// and one more FK behind the last iteration for d_nodes and the residual.  The inputs, 1, the clamped step of 2, 5 and the result
+// are the frame this solver shares with fit.hip: pose_solve.h has them, here are 3 and 4.
 //
 // ONE workgroup per problem, ALL iterations in one launch: thread j owns joint j and keeps its quaternion in registers.
 // J <= 64: one wave64 on fk_wave_*; 65 .. 256: 256 threads on fk_block_*.  The topology (levels, children; each handle's ancestor
@@ -24,9 +25,7 @@
 // shuffle) follow; their barriers are passed by every thread of the workgroup.
 // What bounds it is the chain of dependent steps (depth levels per sweep, 3E steps per factorisation and per solve, times the
 // iterations), not bytes: a problem reads and writes a few KiB once.
-#include "fk_device.h"
-
-#include <type_traits>
+#include "pose_solve.h"
 
 namespace riggs {
 
@@ -34,11 +33,9 @@ namespace riggs {
 #define IK_MAX_N (3 * IK_MAX_E)
 
 struct IkArgs {
-  int J, E, iterations, relative, solve_translation;
-  float damping, max_step;
-  const float* joints; const int32_t* parents; const float* local_rot_in; const float* global_trans_in;
-  const int32_t* handles; const float* targets; const float* weights; const uint8_t* locked; const float* extent;
-  float* local_rot_out; float* global_trans_out; float* d_nodes; float* residual;
+  SolveArgs s;
+  int E;
+  const int32_t* handles; const float* targets; const float* weights;
 };
 
 struct IkShared {
@@ -56,36 +53,18 @@ template <bool WIDE>
 __global__ __launch_bounds__(WIDE ? 256 : 64) void ik_solve_kernel(IkArgs a) {
   constexpr int NT = WIDE ? 256 : 64, NW = NT / RIGGS_WAVE;
   __shared__ IkShared sh;
-  __shared__ typename std::conditional<WIDE, FkWideShared, int>::type wsh;
-  typedef typename std::conditional<WIDE, FkWide, FkLane>::type Fk;
+  __shared__ typename SolveChain<WIDE>::Shared wsh;
   const int b = blockIdx.x, j = threadIdx.x, lane = j & (RIGGS_WAVE - 1), wave = j / RIGGS_WAVE;
-  const int J = a.J, E = a.E, n = 3 * E;
+  const int J = a.s.J, E = a.E, n = 3 * E;
   const bool on = j < J;
 
-  // ---- the problem's inputs.  A parent outside [0, j) is clamped into it: the walks below end and no index leaves the arrays.
-  FkIn in = {};
-  in.q[0] = 1.f;
-  bool locked = false;
-  if (on) {
-    int vp = 0;
-    if (j >= 1) vp = min(max(a.parents[j], 0), j - 1);
-    in.par = vp;
-#pragma unroll
-    for (int e = 0; e < 4; e++) in.q[e] = a.local_rot_in[((size_t)b * J + j) * 4 + e];
-#pragma unroll
-    for (int e = 0; e < 3; e++) { in.x[e] = a.joints[3 * j + e]; in.c[e] = a.joints[3 * vp + e]; }
-    locked = a.locked && a.locked[j] != 0;
-  }
-  for (int i = j; i < MAX_J_WIDE; i += NT) sh.par[i] = 0;
+  // ---- the problem's inputs (the parents clamped: the walks below end); extent == NULL: 1
+  SolveIn pr;
   float gt[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) gt[c] = a.global_trans_in[(size_t)b * 3 + c];
-  const float ext = a.extent ? a.extent[0] : 1.f;
-  const float damping = (a.relative & 1) ? a.damping * ext : a.damping;
-  const float max_step = (a.relative & 2) ? a.max_step * ext : a.max_step;
-  const float damping2 = damping * damping;
+  solve_load(a.s, b, j, a.s.extent ? a.s.extent[0] : 1.f, pr, gt);
+  for (int i = j; i < MAX_J_WIDE; i += NT) sh.par[i] = 0;
   __syncthreads();
-  if (on) sh.par[j] = in.par;
+  if (on) sh.par[j] = pr.in.par;
   if (j < IK_MAX_E) {
     int h = -1, live = 0;
     float s = 0.f;
@@ -115,49 +94,23 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void ik_solve_kernel(IkArgs a) {
   uint32_t mine = 0u;  // bit e: this thread's joint turns handle e
 #pragma unroll
   for (int e = 0; e < IK_MAX_E; e++)
-    if (e < E && on && !locked && (sh.path[e][j >> 5] >> (j & 31) & 1u)) mine |= 1u << e;
+    if (e < E && on && !pr.locked && (sh.path[e][j >> 5] >> (j & 31) & 1u)) mine |= 1u << e;
 
   // ---- topology and the first sweep
-  Fk f;
-  if constexpr (WIDE) fk_block_forward(J, in, f, wsh);
-  else fk_wave_forward(J, in, f);
+  typedef SolveChain<WIDE> Chain;
+  typename Chain::Fk f;
+  Chain::forward(J, pr.in, f, wsh);
 
   for (int it = 0;; it++) {
-    if (it > 0) {
-      if constexpr (WIDE) fk_block_sweep(J, in, f, wsh);
-      else fk_wave_sweep(J, in, f);
-    }
-    float G[12];
-#pragma unroll
-    for (int e = 0; e < 12; e++) {
-      if constexpr (WIDE) G[e] = wsh.G[j][e];
-      else G[e] = f.G[e];
-    }
-    if (on) {
-#pragma unroll
-      for (int r = 0; r < 3; r++)  // (fk_forward_kernel's d_nodes, operation for operation)
-        sh.pos[j][r] = (G[4 * r] * in.x[0] + G[4 * r + 1] * in.x[1] + G[4 * r + 2] * in.x[2] + G[4 * r + 3]) + gt[r];
-    }
+    if (it > 0) Chain::sweep(J, pr.in, f, wsh);
+    Chain::posed(f, wsh, pr, gt, on, sh.pos[j]);
     __syncthreads();
-    if (it >= a.iterations) break;
+    if (it >= a.s.iterations) break;
 
     // ---- 2: the right-hand side, one thread per handle
     if (j < IK_MAX_E) {
       float r[3] = {0.f, 0.f, 0.f};
-      if (j < E && sh.live[j]) {
-        const int h = sh.handle[j];
-        float d[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) d[c] = sh.target[j][c] - sh.pos[h][c];
-        const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (len > max_step) {
-          const float k = max_step / len;
-#pragma unroll
-          for (int c = 0; c < 3; c++) d[c] = d[c] * k;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; c++) r[c] = sh.s[j] * d[c];
-      }
+      if (j < E && sh.live[j]) clamped_step(sh.target[j], sh.pos[sh.handle[j]], pr.max_step, sh.s[j], r);
 #pragma unroll
       for (int c = 0; c < 3; c++) sh.rhs[3 * j + c] = r[c];
     }
@@ -166,7 +119,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void ik_solve_kernel(IkArgs a) {
     {
       float piv[3];
 #pragma unroll
-      for (int c = 0; c < 3; c++) piv[c] = sh.pos[in.par][c];
+      for (int c = 0; c < 3; c++) piv[c] = sh.pos[pr.in.par][c];
 #pragma unroll
       for (int e = 0; e < IK_MAX_E; e++) {
         const int h = (mine >> e & 1u) ? sh.handle[e] : 0;
@@ -200,8 +153,8 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void ik_solve_kernel(IkArgs a) {
       for (int w = 0; w < NW; w++) v += (e <= g) ? sh.part[w][e * IK_MAX_E + g][3 * r + c] : sh.part[w][g * IK_MAX_E + e][3 * c + r];
       const float ss = sh.s[e] * sh.s[g];
       v = ss * v;
-      if (a.solve_translation && r == c) v += ss;
-      if (row == col) v += damping2;
+      if (a.s.solve_translation && r == c) v += ss;
+      if (row == col) v += pr.damping2;
       sh.A[row][col] = v;
     }
     __syncthreads();
@@ -243,49 +196,14 @@ __global__ __launch_bounds__(WIDE ? 256 : 64) void ik_solve_kernel(IkArgs a) {
         if (sh.live[e]) { dgt[0] = dgt[0] + s * y0; dgt[1] = dgt[1] + s * y1; dgt[2] = dgt[2] + s * y2; }
       }
     }
-    float Rp[9];  // the parent's rotation (the lane shuffles are taken by every lane)
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        if constexpr (WIDE) Rp[3 * r + c] = wsh.G[in.par][4 * r + c];
-        else Rp[3 * r + c] = fk_lane_get(f.G[4 * r + c], in.par);
-      }
-    float dl[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) dl[c] = (j == 0) ? om[c] : Rp[c] * om[0] + Rp[3 + c] * om[1] + Rp[6 + c] * om[2];
-    const float th = sqrtf(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
-    if (on && mine != 0u && th > 0.f) {
-      const float half = 0.5f * th, k = sinf(half) / th;
-      const float aw = cosf(half), ax = k * dl[0], ay = k * dl[1], az = k * dl[2];
-      const float bw = in.q[0], bx = in.q[1], by = in.q[2], bz = in.q[3];
-      in.q[0] = aw * bw - ax * bx - ay * by - az * bz;
-      in.q[1] = aw * bx + ax * bw + ay * bz - az * by;
-      in.q[2] = aw * by - ax * bz + ay * bw + az * bx;
-      in.q[3] = aw * bz + ax * by - ay * bx + az * bw;
-    }
-    if (a.solve_translation) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) gt[c] = gt[c] + dgt[c];
-    }
+    Chain::turn(f, wsh, om, on && mine != 0u, a.s.solve_translation != 0, dgt, pr, gt);
   }
 
   // ---- the result (sh.pos is the posed skeleton of the final quaternions, behind a barrier)
-  if (on) {
-#pragma unroll
-    for (int e = 0; e < 4; e++) a.local_rot_out[((size_t)b * J + j) * 4 + e] = in.q[e];
-#pragma unroll
-    for (int c = 0; c < 3; c++) a.d_nodes[((size_t)b * J + j) * 3 + c] = sh.pos[j][c];
-  }
-  if (j < 3) a.global_trans_out[(size_t)b * 3 + j] = gt[j];
+  solve_write(a.s, b, j, pr, gt, sh.pos);
   if (j < E) {
-    const int h = sh.handle[j];
-    float res = __builtin_nanf("");  // (a handle index outside [0, J): there is no position to measure)
-    if (h >= 0) {
-      const float d0 = sh.target[j][0] - sh.pos[h][0], d1 = sh.target[j][1] - sh.pos[h][1], d2 = sh.target[j][2] - sh.pos[h][2];
-      res = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-    }
-    a.residual[(size_t)b * E + j] = res;
+    const int h = sh.handle[j];  // (a handle index outside [0, J): there is no position to measure)
+    a.s.residual[(size_t)b * E + j] = h >= 0 ? solve_distance(sh.target[j], sh.pos[h]) : __builtin_nanf("");
   }
 }
 
@@ -300,20 +218,13 @@ int riggs_ik_solve(int32_t B, int32_t J, int32_t E, const float* joints, const i
                    const uint8_t* locked, int32_t iterations, float damping, float max_step, const float* extent, int32_t relative,
                    int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
                    riggs_stream stream) {
-  RIGGS_REQUIRE(B >= 1, "riggs_ik_solve: needs B >= 1");
-  RIGGS_REQUIRE(J >= 1 && J <= MAX_J_WIDE, "riggs_ik_solve: num_joints must be in [1, 256]");
-  RIGGS_REQUIRE(E >= 1 && E <= IK_MAX_E, "riggs_ik_solve: 1 to RIGGS_IK_MAX_HANDLES handles");
-  RIGGS_REQUIRE(iterations >= 0, "riggs_ik_solve: iterations >= 0");
-  RIGGS_REQUIRE((relative & ~3) == 0 && (relative == 0 || extent), "riggs_ik_solve: relative is a mask of bits 0 and 1 and needs extent");
-  RIGGS_REQUIRE(damping > 0.f && max_step >= 0.f, "riggs_ik_solve: needs damping > 0 and max_step >= 0");  // (a NaN fails both)
-  RIGGS_REQUIRE(joints && parents && local_rot_in && global_trans_in && handles && targets && local_rot_out && global_trans_out &&
-                    d_nodes && residual, "riggs_ik_solve: NULL argument");
   IkArgs a;
-  a.J = J; a.E = E; a.iterations = iterations; a.relative = relative; a.solve_translation = solve_translation != 0;
-  a.damping = damping; a.max_step = max_step;
-  a.joints = joints; a.parents = parents; a.local_rot_in = local_rot_in; a.global_trans_in = global_trans_in;
-  a.handles = handles; a.targets = targets; a.weights = weights; a.locked = locked; a.extent = extent;
-  a.local_rot_out = local_rot_out; a.global_trans_out = global_trans_out; a.d_nodes = d_nodes; a.residual = residual;
+  if (int rc = solve_args("riggs_ik_solve", B, J, joints, parents, local_rot_in, global_trans_in, locked, iterations, damping, max_step,
+                          extent, relative, solve_translation, local_rot_out, global_trans_out, d_nodes, residual, a.s)) return rc;
+  RIGGS_REQUIRE(E >= 1 && E <= IK_MAX_E, "riggs_ik_solve: 1 to RIGGS_IK_MAX_HANDLES handles");
+  RIGGS_REQUIRE(relative == 0 || extent, "riggs_ik_solve: a relative damping or max_step needs extent");
+  RIGGS_REQUIRE(handles && targets, "riggs_ik_solve: NULL argument");
+  a.E = E; a.handles = handles; a.targets = targets; a.weights = weights;
   if (J <= MAX_J) hipLaunchKernelGGL(ik_solve_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(ik_solve_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
   RIGGS_HIP_CHECK(hipGetLastError());

@@ -7,9 +7,6 @@ margin of 8 stands for the hardware's sin / cos / sqrt and whatever order of ope
 tests/test_fit_ref_cpu.py holds e32 <= 1e-4 on every case.  REACH: residual <= max(4 * r32, 1e-5 * extent) after 32 iterations,
 r32 the float32 restatement's residual.  With RIGGS_FIT_PARITY_JSON set to a path, what was measured is written there
 (profiles/fit_parity.json is such a record)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -21,16 +18,23 @@ from riggs_amd import pose_edit as PE  # noqa: E402
 from tests import fit_ref as F  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
 from tests import ik_ref as R  # noqa: E402
+from tests.pose_solve_util import T, bits, deviation, make_rig, parity_bars, parity_report  # noqa: E402
 
 COUNTS = F.SNAPSHOTS
 KEYS = ("local_rotation", "global_trans", "d_nodes", "residual")
 PARAMS = [(name, B) for name in F.PARITY for B in (1, 3)]
 IDS = ["%s-B%d" % p for p in PARAMS]
+# What the solver's frame (csrc/pose_solve.h) does in each of its two forms (one wave: two_joints; 256 threads: tree65) and no case
+# above asks of it (NOTES.md has the table): absolute damping and max_step (relative = 0), one of the two (relative = 1, 2), the
+# translation solved for beyond one joint; and of the solver's own, one CG step on 256 threads and more CG steps than joints.
+# 3 problems, FEATURE_COUNTS iterations, the bars of the cases above.
+FEATURES = {"absolute": dict(damping=0.07, max_step=0.6), "max_step": dict(max_step=0.6), "damping": dict(damping=0.07),
+            "translation": dict(solve_translation=True), "one_cg_step": dict(cg_steps=1), "cg_steps_over_J": dict(cg_steps=8)}
+FEATURE_COUNTS = (1, 4)
+FEATURE_PARAMS = [(name, 3, f) for f in FEATURES for name in ("two_joints", "tree65")
+                  if (name, f) not in (("two_joints", "one_cg_step"), ("tree65", "cg_steps_over_J"))]
 _GPU, _REPORT = {}, {}
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+report = parity_report("RIGGS_FIT_PARITY_JSON", _REPORT)
 
 
 def run(case, iterations, **kw):
@@ -46,51 +50,37 @@ def run(case, iterations, **kw):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def reference(name, B):
+def reference(name, B, feature=None):
     """(case, float64 snapshots, float32 snapshots, GPU results) per iteration count: computed once, shared, never changed."""
-    case, o64, o32 = F.reference(name, B)
-    if (name, B) not in _GPU:
-        _GPU[(name, B)] = {n: run(case, n) for n in COUNTS}
-    return case, o64, o32, _GPU[(name, B)]
-
-
-def deviation(a, b, key, extent):
-    d = float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
-    return d if key == "local_rotation" else d / extent
+    if (name, B, feature) not in _GPU:
+        if feature is None:
+            case, o64, o32 = F.reference(name, B)
+            kw, counts = {}, COUNTS
+        else:
+            case, kw, counts = F.make_case(name, B), FEATURES[feature], FEATURE_COUNTS
+            o64 = F.solve_case(case, max(counts), np.float64, snapshots=counts, **kw)
+            o32 = F.solve_case(case, max(counts), np.float32, snapshots=counts, **kw)
+        _GPU[(name, B, feature)] = (case, o64, o32, {n: run(case, n, **kw) for n in counts})
+    return _GPU[(name, B, feature)]
 
 
 def bars_of(o64, o32, extent):
-    e32 = {k: deviation(o32[k], o64[k], k, extent) for k in KEYS}
-    return {k: max(8 * e32[k], 1e-6) for k in KEYS}, e32
+    return parity_bars(o64, o32, KEYS, extent)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def report():
-    yield
-    path = os.environ.get("RIGGS_FIT_PARITY_JSON")
-    if _REPORT and path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(_REPORT, f, indent=1, sort_keys=True)
-
-
-@pytest.mark.parametrize("name,B", PARAMS, ids=IDS)
-def test_parity_with_the_float64_oracle(name, B):
-    case, o64, o32, gpu = reference(name, B)
+@pytest.mark.parametrize("name,B,feature", [p + (None,) for p in PARAMS] + FEATURE_PARAMS, ids=IDS + ["%s-B%d-%s" % p for p in FEATURE_PARAMS])
+def test_parity_with_the_float64_oracle(name, B, feature):
+    case, o64, o32, gpu = reference(name, B, feature)
     failed = []
-    for n in COUNTS:
+    for n in sorted(gpu):
         bar, e32 = bars_of(o64[n], o32[n], case["extent"])
         dev = {k: deviation(gpu[n][k], o64[n][k], k, case["extent"]) for k in KEYS}
-        _REPORT["%s-B%d-it%d" % (name, B, n)] = {"e32": e32, "gpu": dev, "bar": bar,
+        _REPORT["%s-B%d-it%d" % ("-".join(filter(None, (name, feature))), B, n)] = {"e32": e32, "gpu": dev, "bar": bar,
                                                "gpu_over_e32": {k: (dev[k] / e32[k] if e32[k] > 0 else None) for k in KEYS},
                                                "residual_over_extent": {"float64": float(o64[n]["residual"].max() / case["extent"]),
                                                                         "float32": float(o32[n]["residual"].max() / case["extent"]),
                                                                         "gpu": float(gpu[n]["residual"].max() / case["extent"])}}
-        print(name, B, n, "e32", e32, "gpu", dev)
+        print(name, B, feature, n, "e32", e32, "gpu", dev)
         failed += ["%s after %d iterations: %.3g > %.3g (e32 %.3g)" % (k, n, dev[k], bar[k], e32[k]) for k in KEYS if not dev[k] <= bar[k]]
     assert not failed, "; ".join(failed)
 
@@ -215,15 +205,6 @@ def test_unreachable_targets_stay_finite_and_translation_brings_them_back():
     got = np.asarray(run(case, 32, targets=far, solve_translation=True)["residual"], np.float64)
     print("tree8 shifted by 10 extents, solve_translation: residual / extent gpu", got.max() / ext, "float32", r32.max() / ext)
     assert np.isfinite(got).all() and (got <= np.maximum(4 * r32, 1e-5 * ext)).all(), (got, r32)
-
-
-def make_rig(case):
-    from riggs_amd.skeleton import SkeletonWarp
-    sw = SkeletonWarp(is_blender=True, joints=torch.from_numpy(case["joints"]), parent_indices=torch.from_numpy(case["parents"]).long(),
-                      K=-1, hyper_dim=8, use_skinning_weight_mlp=False, use_template_offsets=False).cuda()
-    g = torch.Generator().manual_seed(5)
-    x = (torch.from_numpy(case["joints"])[torch.randint(0, case["J"], (500,), generator=g)] + 0.05 * torch.randn(500, 3, generator=g)).cuda()
-    return sw, x
 
 
 @pytest.mark.parametrize("name", ["tree24", "tree65"])

@@ -6,9 +6,6 @@ Bars.  PARITY per case and tensor: max(8 * e32, 1e-6), e32 = the float32 restate
 hardware's sin / cos / sqrt.  REACH: residual <= max(4 * r32, 1e-5 * extent) after 32 iterations, r32 the float32 restatement's
 residual; the floor stands for a few float32 roundings through a chain of about 20 levels.  With RIGGS_IK_PARITY_JSON set to a
 path, what was measured is written there (profiles/ik_parity.json is such a record)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -19,16 +16,22 @@ from riggs_amd import _lib as L  # noqa: E402
 from riggs_amd import pose_edit as PE  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
 from tests import ik_ref as R  # noqa: E402
+from tests.pose_solve_util import T, bits, deviation, make_rig, parity_bars, parity_report  # noqa: E402
 
 COUNTS = (8, 32)
 KEYS = ("local_rotation", "global_trans", "d_nodes")
 PARAMS = [(name, B) for name in R.CASES for B in (1, 3)]
 IDS = ["%s-B%d" % p for p in PARAMS]
+# What the solver's frame (csrc/pose_solve.h) does in each of its two forms (one wave: two_joints; 256 threads: tree65) and no case
+# above asks of it (NOTES.md has the table): absolute damping and max_step (relative = 0: extent is NULL), one of the two (relative
+# = 1, 2), the translation solved for beyond one joint, one handle on 256 threads.  3 problems, FEATURE_COUNTS iterations, the
+# bars of the cases above.
+FEATURES = {"absolute": dict(damping=0.07, max_step=0.6), "max_step": dict(max_step=0.6), "damping": dict(damping=0.07),
+            "translation": dict(solve_translation=True), "one_handle": dict(E=1)}
+FEATURE_COUNTS = (1, 4)
+FEATURE_PARAMS = [(name, 3, f) for f in FEATURES for name in ("two_joints", "tree65") if (name, f) != ("two_joints", "one_handle")]
 _CACHE, _REPORT = {}, {}
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+report = parity_report("RIGGS_IK_PARITY_JSON", _REPORT)
 
 
 def run(case, iterations, **kw):
@@ -44,51 +47,46 @@ def run(case, iterations, **kw):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def reference(name, B):
+def feature_case(name, B, feature):
+    """(the case with a FEATURES entry applied, what of the entry goes to the solver as keywords)."""
+    case, kw = R.make_case(name, B), dict(FEATURES[feature] if feature else {})
+    if kw.pop("E", None):
+        case = dict(case, handles=case["handles"][:1], targets=np.ascontiguousarray(case["targets"][:, :1]), E=1)
+    if kw.pop("solve_translation", False):
+        case = dict(case, solve_translation=True)
+    return case, kw
+
+
+def reference(name, B, feature=None):
     """(case, float64 snapshots, float32 snapshots, GPU results) per iteration count: computed once, shared, never changed."""
-    if (name, B) not in _CACHE:
-        case = R.make_case(name, B)
-        o64 = R.solve_case(case, max(COUNTS), np.float64, snapshots=COUNTS)
-        o32 = R.solve_case(case, max(COUNTS), np.float32, snapshots=COUNTS)
-        gpu = {n: run(case, n) for n in COUNTS}
-        _CACHE[(name, B)] = (case, o64, o32, gpu)
-    return _CACHE[(name, B)]
+    if (name, B, feature) not in _CACHE:
+        case, kw = feature_case(name, B, feature)
+        counts = FEATURE_COUNTS if feature else COUNTS
+        o64 = R.solve_case(case, max(counts), np.float64, snapshots=counts, **kw)
+        o32 = R.solve_case(case, max(counts), np.float32, snapshots=counts, **kw)
+        gpu = {n: run(case, n, **kw) for n in counts}
+        _CACHE[(name, B, feature)] = (case, o64, o32, gpu)
+    return _CACHE[(name, B, feature)]
 
 
-def deviation(a, b, key, extent):
-    d = float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
-    return d if key == "local_rotation" else d / extent
-
-
-def bars(name, B, n):
+def bars(name, B, n, feature=None):
     """The parity bar of every tensor after n iterations, and e32 behind it."""
-    case, o64, o32, _ = reference(name, B)
-    e32 = {k: deviation(o32[n][k], o64[n][k], k, case["extent"]) for k in KEYS}
-    return {k: max(8 * e32[k], 1e-6) for k in KEYS}, e32
+    case, o64, o32, _ = reference(name, B, feature)
+    return parity_bars(o64[n], o32[n], KEYS, case["extent"])
 
 
-@pytest.fixture(scope="module", autouse=True)
-def report():
-    yield
-    path = os.environ.get("RIGGS_IK_PARITY_JSON")
-    if _REPORT and path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(_REPORT, f, indent=1, sort_keys=True)
-
-
-@pytest.mark.parametrize("name,B", PARAMS, ids=IDS)
-def test_parity_with_the_float64_oracle(name, B):
-    case, o64, o32, gpu = reference(name, B)
+@pytest.mark.parametrize("name,B,feature", [p + (None,) for p in PARAMS] + FEATURE_PARAMS, ids=IDS + ["%s-B%d-%s" % p for p in FEATURE_PARAMS])
+def test_parity_with_the_float64_oracle(name, B, feature):
+    case, o64, o32, gpu = reference(name, B, feature)
     failed = []
-    for n in COUNTS:
-        bar, e32 = bars(name, B, n)
+    for n in sorted(gpu):
+        bar, e32 = bars(name, B, n, feature)
         dev = {k: deviation(gpu[n][k], o64[n][k], k, case["extent"]) for k in KEYS}
-        _REPORT["%s-B%d-it%d" % (name, B, n)] = {"e32": e32, "gpu": dev, "bar": bar,
+        _REPORT["%s-B%d-it%d" % ("-".join(filter(None, (name, feature))), B, n)] = {"e32": e32, "gpu": dev, "bar": bar,
                                                "residual_over_extent": {"float64": float(o64[n]["residual"].max() / case["extent"]),
                                                                         "float32": float(o32[n]["residual"].max() / case["extent"]),
                                                                         "gpu": float(gpu[n]["residual"].max() / case["extent"])}}
-        print(name, B, n, "e32", e32, "gpu", dev)
+        print(name, B, feature, n, "e32", e32, "gpu", dev)
         failed += ["%s after %d iterations: %.3g > %.3g (e32 %.3g)" % (k, n, dev[k], bar[k], e32[k]) for k in KEYS if not dev[k] <= bar[k]]
     assert not failed, "; ".join(failed)
 
@@ -103,10 +101,6 @@ def test_reach(name, B):
     # residual is |target - posed handle| of the returned skeleton
     mine = np.sqrt(((case["targets"] - gpu[32]["d_nodes"][:, case["handles"]]) ** 2).sum(-1))
     assert np.abs(mine - got).max() <= 1e-6 * max(1.0, float(np.abs(case["targets"]).max()))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("name", ["tree24", "tree65"])
@@ -214,15 +208,6 @@ def test_an_unreachable_target_stays_finite():
         assert (norm(r32["residual"]) <= norm(r8["residual"])).all(), name
 
 
-def make_rig(case):
-    from riggs_amd.skeleton import SkeletonWarp
-    sw = SkeletonWarp(is_blender=True, joints=torch.from_numpy(case["joints"]), parent_indices=torch.from_numpy(case["parents"]).long(),
-                      K=-1, hyper_dim=8, use_skinning_weight_mlp=False, use_template_offsets=False).cuda()
-    g = torch.Generator().manual_seed(5)
-    x = (torch.from_numpy(case["joints"])[torch.randint(0, case["J"], (500,), generator=g)] + 0.05 * torch.randn(500, 3, generator=g)).cuda()
-    return sw, x
-
-
 @pytest.mark.parametrize("name", ["tree24", "tree65"])
 def test_the_pose_goes_through_the_rig(name):
     from riggs_amd import synth
@@ -303,11 +288,16 @@ def test_refusals():
     torch.cuda.synchronize()
     assert bool((buf == U.SENT).all())
     # a handle index outside [0, J) that lives on the device is not read back: the kernel switches it off, its residual is NaN
-    dev_handles = T(np.array([case["handles"][0], case["J"] + 5, case["handles"][2]], np.int32))
-    got = PE.solve_ik(rig, pose, dev_handles, tgt, iterations=8)
-    w = torch.tensor([1.0, 0.0, 1.0], device="cuda")
-    ref = PE.solve_ik(rig, pose, T(case["handles"]), tgt, weights=w, iterations=8)
-    assert torch.equal(got["local_rotation"], ref["local_rotation"]) and bool(torch.isnan(got["residual"][1]))
+    # (on one wave and on 256 threads)
+    for case in (case, R.make_case("tree65", 1)):
+        rig = (T(case["joints"]), T(case["parents"]))
+        pose = {"local_rotation": T(case["q0"][0]), "global_trans": T(case["gt0"])}
+        tgt = T(case["targets"][0, :3])
+        dev_handles = T(np.array([case["handles"][0], case["J"] + 5, case["handles"][2]], np.int32))
+        got = PE.solve_ik(rig, pose, dev_handles, tgt, iterations=8)
+        w = torch.tensor([1.0, 0.0, 1.0], device="cuda")
+        ref = PE.solve_ik(rig, pose, T(case["handles"][:3]), tgt, weights=w, iterations=8)
+        assert torch.equal(got["local_rotation"], ref["local_rotation"]) and bool(torch.isnan(got["residual"][1]))
 
 
 def test_the_edit_step_on_the_device_is_the_one_on_the_host():

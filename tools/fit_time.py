@@ -10,54 +10,17 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from riggs_amd import pose_edit as PE  # noqa: E402
-from riggs_amd.dual_quaternion import quaternion_raw_multiply, quaternion_to_matrix  # noqa: E402
+from pose_solve_common import TorchChain, make_problem, timed  # noqa: E402  (tools/ is the script's directory)
 
 
-def make_problem(J, B, seed):
-    """A random tree (parents[i] = randint(0, i), bone offsets N(0, 0.25^2)), a starting pose identity + N(0, 0.1^2) and a second
-    pose identity + N(0, 0.25^2) whose posed joints are the targets."""
-    rng = np.random.default_rng(seed)
-    parents = np.zeros(J, np.int64)
-    joints = np.zeros((J, 3), np.float32)
-    depth = np.zeros(J, np.int64)
-    for i in range(1, J):
-        parents[i] = rng.integers(0, i)
-        joints[i] = joints[parents[i]] + rng.normal(0, 0.25, 3)
-        depth[i] = depth[parents[i]] + 1
-    ident = np.array([1, 0, 0, 0], np.float32)
-    q0 = (ident + rng.normal(0, 0.1, (B, J, 4))).astype(np.float32)
-    q1 = (ident + rng.normal(0, 0.25, (B, J, 4))).astype(np.float32)
-    return joints, parents, depth, q0, q1
-
-
-class TorchFit:
+class TorchFit(TorchChain):
     """The iteration of include/riggs_hip.h (riggs_fit_pose) in torch ops, all weights 1, no locked joint, no translation."""
-
-    def __init__(self, joints, parents, depth, dev):
-        self.J = len(parents)
-        self.x = torch.tensor(joints, device=dev)
-        self.vp = torch.tensor(parents, device=dev)
-        self.c = self.x[self.vp]
-        self.levels = [torch.tensor(np.flatnonzero(depth == l), device=dev) for l in range(1, int(depth.max()) + 1)]
-        self.level_parents = [self.vp[idx] for idx in self.levels]
-        ext = PE.rig_extent(self.x)
-        self.damping2, self.max_step = (0.05 * ext) ** 2, 0.5 * ext
-
-    def fk(self, q, gt):
-        R = quaternion_to_matrix(q)                                            # (B, J, 3, 3)
-        t = self.c - (R @ self.c[None, :, :, None])[..., 0]
-        GR, Gt = R.clone(), t.clone()
-        for idx, p in zip(self.levels, self.level_parents):
-            Gt[:, idx] = (GR[:, p] @ t[:, idx, :, None])[..., 0] + Gt[:, p]
-            GR[:, idx] = GR[:, p] @ R[:, idx]
-        return GR, (GR @ self.x[None, :, :, None])[..., 0] + Gt + gt[:, None]
 
     def prefix(self, v):
         v = v.clone()
@@ -77,9 +40,7 @@ class TorchFit:
             GR, posed = self.fk(q, gt)
             pc = posed - posed[:, :1]
             pv = pc[:, self.vp]
-            d = targets - posed
-            n = d.norm(dim=-1, keepdim=True)
-            rr = torch.where(n > self.max_step, d * (self.max_step / n.clamp_min(1e-30)), d)
+            rr = self.clamped(targets - posed)
             sums = self.subtree(torch.cat([rr, cross(pc, rr), torch.ones_like(pc[..., :1]), pc, (pc * pc).sum(-1, keepdim=True)], -1))
             b = sums[..., 3:6] - cross(pv, sums[..., 0:3])
             dd = (sums[..., 10:11] - 2 * (pv * sums[..., 7:10]).sum(-1, keepdim=True) + (pv * pv).sum(-1, keepdim=True) * sums[..., 6:7]).clamp_min(0)
@@ -103,26 +64,8 @@ class TorchFit:
                 rzn = (r * z).sum((1, 2), keepdim=True)
                 p = z + (rzn / rz.clamp_min(1e-38)) * p
                 rz = rzn
-            delta = (GR[:, self.vp].transpose(2, 3) @ x[..., None])[..., 0]
-            delta = torch.cat([x[:, :1], delta[:, 1:]], 1)
-            th = delta.norm(dim=-1, keepdim=True)
-            kk = torch.sin(0.5 * th) / th.clamp_min(1e-30)
-            dq = torch.cat([torch.cos(0.5 * th), kk * delta], -1)
-            q = torch.where(th > 0, quaternion_raw_multiply(dq, q), q)
+            q = self.turn(q, GR, x)
         return q, self.fk(q, gt)[1]
-
-
-def timed(fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():
