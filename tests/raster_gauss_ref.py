@@ -360,10 +360,12 @@ def _cov2d(A, p, c6, V, fx, fy, tanx, tany):
     return o
 
 
-def kernel_steps(A, t, cfg, rec=None, clamp_bits=None, fault=None):
+def kernel_steps(A, t, cfg, rec=None, clamp_bits=None, fault=None, rec_err=None):
     """The steps of preprocess_fwd (and, with a record ``rec`` (N, 10), of preprocess_bwd's bwd_math + bwd_outputs) over the
     arithmetic ``A``.  ``t``: the case's CPU tensors (tests/test_gpu_raster_gauss_f64.build), ``cfg``: its dict.  ``clamp_bits``:
     the clamp bits the backward reads ((N,) uint8; default: the ones this forward computes).  ``fault``: one of FAULTS.
+    ``rec_err`` (with the Bounded arithmetic): a bound (N, 10) of what the record the kernel reads may differ from ``rec`` — a record
+    that is itself a computed quantity (tests/raster_comp_ref.py: the compositing backward's sums) instead of an injected one.
     Returns a dict of arithmetic values (lists per column); rows that are not visible hold garbage."""
     assert fault is None or fault in FAULTS
     glue, iso, deg, mod = cfg["glue"], cfg.get("iso", False), cfg["deg"], cfg.get("mod", 1.0)
@@ -460,6 +462,8 @@ def kernel_steps(A, t, cfg, rec=None, clamp_bits=None, fault=None):
     # ---- bwd_math
     cl = o["clamped"] if clamp_bits is None else torch.stack([(clamp_bits.long() >> c) & 1 for c in range(3)], 1).bool()
     g = col(rec, 10)
+    if rec_err is not None:
+        g = [Er(x.v, rec_err[:, j].to(F64)) for j, x in enumerate(g)]
     g2x, g2y, gA, gB, gC, g_op, gd = g[0], g[1], g[2], g[3], g[4], g[5], g[9]
     gcol = g[6:9]
     if fault == "conic_B_halved":
@@ -689,13 +693,13 @@ def reference(t, cfg, rec=None, vis=None, clamp_bits=None):
 
 
 # ------------------------------------------------------------------------------------------------ bounds
-def bounds(t, cfg, rec=None, vis=None, clamp_bits=None):
+def bounds(t, cfg, rec=None, vis=None, clamp_bits=None, rec_err=None):
     """(values, error bounds, ambiguous) of the kernel's steps: ``values`` the float64 evaluation of the kernel's own formulas (a
     second opinion of ``reference``), ``error bounds`` per element as the module's docstring derives them; exact-zero rules applied.
     ``ambiguous`` (N,) bool: a recomputed decision within its error of its threshold."""
     A = Bounded()
     with torch.no_grad():
-        o = kernel_steps(A, t, cfg, rec=rec, clamp_bits=clamp_bits)
+        o = kernel_steps(A, t, cfg, rec=rec, clamp_bits=clamp_bits, rec_err=rec_err)
         sel = None
         if rec is not None:
             sel = vis & (rec != 0).any(1)
@@ -713,7 +717,7 @@ def bounds(t, cfg, rec=None, vis=None, clamp_bits=None):
     if rec is not None:
         # pass-through outputs: the record's numbers bit for bit
         for k in ("dL_dmeans2D", "dL_dcolors_precomp") + (() if cfg["glue"] else ("dL_dopacities",)):
-            if k in err:
+            if k in err and rec_err is None:  # (with ``rec_err`` they carry the record's own bound)
                 err[k] = torch.zeros_like(err[k])
         for k in GRAD_KEYS:
             if k in err:
