@@ -1319,6 +1319,41 @@ int riggs_fit_pose(int32_t B, int32_t J, const float* joints, const int32_t* par
                    int32_t solve_translation, float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual,
                    riggs_stream stream);
 
+/* =====================================================================
+ * Bone-direction fitting (csrc/bones.hip; riggs_amd/pose_edit.py: fit_bones, retarget): every bone h >= 1 (joint h and its parent)
+ * may have a target DIRECTION, which does not depend on the proportions of the skeleton it was taken from: a motion-capture clip,
+ * another rig's track, a rest skeleton extracted anew.  riggs_fit_pose's method on the unit bone vectors: Levenberg-Marquardt with
+ * the clamped step, the damped normal equations solved matrix-free by Jacobi-preconditioned conjugate gradients; restated from the
+ * published methods, tests/bones_ref.py is the NumPy restatement.  Added symbol: RIGGS_ABI_VERSION is unchanged.
+ *
+ * joints, parents, B, J (1 .. 256), local_rot_in, global_trans_in, locked and the outputs are riggs_fit_pose's.  directions (B,J,3):
+ * a vector along the target of bone h in row h, of any length; row 0 is never read.  weights (B,J) or NULL (all 1).  Per problem,
+ * once: L_h = |x_h - x_vp(h)|; row h is read only if weights[h] > 0 and L_h > 0; t_h = v_h / |v_h|; the target is live iff also
+ * |v_h| > 0 (a NaN fails every comparison: off); s_h = sqrt(w_h) where live, else 0; S0_a = sum_subtree s_h^2 (a subtree includes
+ * its root), Minv_a = 1 / (2/3 S0_a + damping^2).  damping > 0 and max_step >= 0 are absolute and dimensionless; cg_steps >= 1.
+ * `iterations` >= 0 steps of:
+ *   1  forward kinematics; beta_h = posed_h - posed_vp(h), d_h = beta_h / |beta_h| (live h, else 0);
+ *      r_h = s_h (t_h - d_h, shortened to max_step)
+ *   2  J p:    W_j = W_vp(j) + omega_j (a locked joint's omega is 0), u_h = s_h (W_h x d_h): the rig is rigid, a bone only turns
+ *      J^T u:  g_a = sum_subtree d_h x (s_h u_h) (locked: 0);  A = J^T J + damping^2 I;  a parent adds its children in
+ *              descending index
+ *   3  cg_steps steps of preconditioned conjugate gradients from x = 0 on A x = J^T r, with riggs_fit_pose's two stopping rules
+ *      (r.z > 1e-10 * (r.z at the start); p.Ap > 0) and its dot product: (a0 b0 + a1 b1) + a2 b2 per joint, a balanced binary
+ *      tree over each 64 joints, the (up to four) sums in order
+ *   4  riggs_ik_solve's step 5 with omega_a = x_a
+ * then one more forward kinematics: d_nodes (B,J,3) and residual (B,J) = |t_h - d_h| where the target is live (the chord of two
+ * unit vectors, in [0, 2]), else 0.  global_trans_out is global_trans_in: no translation is solved for.
+ * A locked joint keeps its quaternion bit for bit, as does a joint whose subtree holds no live target.  The twist about a bone is
+ * not observed; it stays where it was up to rounding.
+ * One workgroup per problem, all iterations in ONE launch on `stream` (J <= 64: one wave; else 256 threads); no float atomics:
+ * the same inputs give the same bits, and a problem's result does not depend on the rest of the batch.  Does not allocate, read
+ * back or synchronise: legal inside a stream capture.
+ * ===================================================================== */
+int riggs_fit_bones(int32_t B, int32_t J, const float* joints, const int32_t* parents, const float* local_rot_in,
+                    const float* global_trans_in, const float* directions, const float* weights, const uint8_t* locked,
+                    int32_t iterations, int32_t cg_steps, float damping, float max_step, float* local_rot_out,
+                    float* global_trans_out, float* d_nodes, float* residual, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

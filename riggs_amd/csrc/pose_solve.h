@@ -9,7 +9,7 @@
 //            q_a <- (cos theta/2, sin(theta/2) delta_a / theta) (x) q_a; global_trans += its step                         turn
 //   result   local_rot_out, d_nodes, global_trans_out; the residual |target - posed| (who has none: each solver's rule)   solve_write, solve_distance
 // Both files are built with -ffp-contract=off and -fno-fast-math: a helper that keeps an expression's tree keeps its bits
-// (tools/pose_solve_bits.py; profiles/pose_solve_bits.json).  Included by ik.hip and fit.hip only.
+// (tools/pose_solve_bits.py; profiles/pose_solve_bits.json).  Included by ik.hip, fit.hip and bones.hip (a third solver: its operators) only.
 #pragma once
 #include "fk_device.h"
 

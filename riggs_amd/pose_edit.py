@@ -10,7 +10,9 @@ NumPy, scipy and two read-backs per mouse event; here it is torch ops that never
 1986) with Buss & Kim's clamped target step on the rig's own kinematics, every iteration inside ONE launch of csrc/ik.hip
 (include/riggs_hip.h: riggs_ik_solve; tests/ik_ref.py is the NumPy restatement).  ``fit_pose`` gives EVERY joint a target
 (a reference skeleton, a frame of a clip of joint positions): Levenberg-Marquardt with matrix-free preconditioned conjugate
-gradients in ONE launch of csrc/fit.hip (riggs_fit_pose; tests/fit_ref.py).  Inference only."""
+gradients in ONE launch of csrc/fit.hip (riggs_fit_pose; tests/fit_ref.py).  ``fit_bones`` gives every BONE a target direction,
+which a skeleton of other proportions can supply (csrc/bones.hip, riggs_fit_bones; tests/bones_ref.py); ``bone_directions`` takes
+the directions from another skeleton's joints and ``retarget`` turns a clip of them into a pose track.  Inference only."""
 from __future__ import annotations
 
 import numpy as np
@@ -311,3 +313,152 @@ def fit_pose(skeleton, pose, targets, weights=None, locked=None, iterations=32, 
                                        extent.data_ptr(), relative, int(bool(solve_translation)), q_out.data_ptr(),
                                        gt_out.data_ptr(), d_nodes.data_ptr(), residual.data_ptr(), L.stream_ptr()), "riggs_fit_pose")
     return _solution(batched, q_out, gt_out, d_nodes, residual)
+
+
+# --------------------------------------------------------------------------- bone directions: skeletons of other proportions
+@torch.no_grad()
+def fit_bones(skeleton, pose, directions, weights=None, locked=None, iterations=32, cg_steps=8, damping=0.05, max_step=0.5):
+    """Turn the joints of ``pose`` so that every BONE (joint h >= 1 and its parent) points along its own target direction.  A
+    direction does not depend on the length of the bone it was taken from, so the targets may come from a skeleton of other
+    proportions (a motion-capture clip, another rig's ``d_nodes``, a rest skeleton extracted anew), where position targets that
+    no pose can reach make ``fit_pose`` bend every joint into a compromise.
+
+    ``skeleton``, ``pose``, ``locked``, ``cg_steps`` and the batching are ``fit_pose``'s.  ``directions``: (J, 3) or (B, J, 3), a
+    vector of any length along the target of bone h in row h; row 0 is ignored (the root has no bone).  ``weights`` (J,) or (B, J),
+    all 1 by default.  A bone has no target where its weight is <= 0, where its rest length is 0 or where its target vector has
+    length 0 (or is NaN); without weight or rest length the row of ``directions`` is never read.  ``damping`` (> 0) and
+    ``max_step`` (>= 0) are absolute: they act on unit vectors, whatever the rig's size.  No translation is solved for:
+    ``global_trans`` is returned as it came (``retarget`` sets it from the source's root).
+
+    The method is ``fit_pose``'s on the unit bone vectors; because the rig is rigid a bone only turns, by the sum of the rotation
+    unknowns along its path, so the Jacobian and its transpose are sweeps of 3 values (include/riggs_hip.h states the iteration,
+    tests/bones_ref.py restates it in NumPy).  The twist about a bone is not observed and stays where it was.
+
+    Returns ``{'local_rotation', 'global_trans', 'd_nodes', 'residual'}`` as ``fit_pose`` does, with ``residual`` (..., J) the
+    chord ``|t - d|`` between the target and the posed unit direction (in [0, 2]; 0 where the bone has no target).
+
+    One launch of csrc/bones.hip, allocations through torch only, nothing read back: the call can be captured in a
+    ``torch.cuda.graph`` and replayed after ``directions`` / ``weights`` changed in place."""
+    if int(cg_steps) < 1:
+        raise L.RiggsHipError("fit_bones: cg_steps must be >= 1, got %r" % (cg_steps,))
+    damping, max_step = 0.05 if damping is None else damping, 0.5 if max_step is None else max_step
+    joints, parents, J, q, gt, locked, damping, max_step, _ = _problem("fit_bones", skeleton, pose, locked, iterations, damping, max_step)
+    dev = joints.device
+    directions = L.require_cuda_f32("directions", directions.detach())
+    if directions.dim() not in (2, 3) or tuple(directions.shape[-2:]) != (J, 3):
+        raise L.RiggsHipError("directions has shape %s, expected (%d, 3) or (B, %d, 3)" % (tuple(directions.shape), J, J))
+    if weights is not None:
+        weights = L.require_cuda_f32("weights", weights.detach())
+        if weights.dim() not in (1, 2) or weights.shape[-1] != J:
+            raise L.RiggsHipError("weights has shape %s, expected (%d,) or (B, %d)" % (tuple(weights.shape), J, J))
+    B, batched, full = _batch("fit_bones", q, gt, [(directions, 3), (weights, 2)])
+    qb, gtb, db = full(q, (J, 4)), full(gt, (3,)), full(directions, (J, 3))
+    wb = None if weights is None else full(weights, (J,))
+    f32 = dict(dtype=torch.float32, device=dev)
+    q_out, gt_out = torch.empty(B, J, 4, **f32), torch.empty(B, 3, **f32)
+    d_nodes, residual = torch.empty(B, J, 3, **f32), torch.empty(B, J, **f32)
+    with torch.cuda.device(dev):
+        L.check(L.lib().riggs_fit_bones(B, J, joints.data_ptr(), parents.data_ptr(), qb.data_ptr(), gtb.data_ptr(), db.data_ptr(),
+                                        L.ptr(wb), L.ptr(locked), int(iterations), int(cg_steps), damping, max_step,
+                                        q_out.data_ptr(), gt_out.data_ptr(), d_nodes.data_ptr(), residual.data_ptr(),
+                                        L.stream_ptr()), "riggs_fit_bones")
+    return _solution(batched, q_out, gt_out, d_nodes, residual)
+
+
+def _virtual_parents(parents, dev):
+    """(J,) long on ``dev`` with the kernels' rule: 0 at the root, a value outside [0, i) clamped into it."""
+    p = torch.as_tensor(parents).to(dev).long().reshape(-1)
+    below = (torch.arange(p.numel(), device=dev) - 1).clamp(min=0)
+    return torch.minimum(p.clamp(min=0), below)
+
+
+@torch.no_grad()
+def bone_directions(joints, parents, joint_map=None):
+    """The bones of another skeleton as ``fit_bones`` takes them: ``(directions (..., J, 3), weights (..., J))``.
+
+    ``joints``: (Js, 3) or (T, Js, 3), the SOURCE skeleton's joints (one frame or a clip); ``parents`` (J,): the RIG's parents;
+    ``joint_map`` (J,) integers: the source joint that stands for rig joint h, -1 for none (an index outside [0, Js) counts as
+    none).  Default: the identity, which needs Js == J.  ``directions[h] = src[map[h]] - src[map[vp(h)]]``, and the weight is 1
+    where h >= 1 and both ends are mapped, else 0 (with a zero direction).  Torch ops on ``joints``'s device, nothing read back."""
+    src = joints.detach().float()
+    if src.dim() not in (2, 3) or src.shape[-1] != 3:
+        raise L.RiggsHipError("bone_directions: joints has shape %s, expected (Js, 3) or (T, Js, 3)" % (tuple(src.shape),))
+    dev, Js = src.device, int(src.shape[-2])
+    vp = _virtual_parents(parents, dev)
+    J = int(vp.numel())
+    idx = torch.arange(J, device=dev)
+    if joint_map is None:
+        if Js != J:
+            raise L.RiggsHipError("bone_directions: %d source joints for %d rig joints need a joint_map" % (Js, J))
+        m = idx
+    else:
+        m = torch.as_tensor(joint_map).to(dev).long().reshape(-1)
+        if m.numel() != J:
+            raise L.RiggsHipError("bone_directions: joint_map has %d entries for %d rig joints" % (m.numel(), J))
+    if Js < 1:
+        raise L.RiggsHipError("bone_directions: the source has no joints")
+    mapped = (m >= 0) & (m < Js)
+    mc = m.clamp(0, Js - 1)
+    ok = mapped & mapped[vp] & (idx >= 1)
+    d = src.index_select(-2, mc) - src.index_select(-2, mc[vp])
+    d = torch.where(ok[:, None], d, torch.zeros_like(d))
+    return d, ok.to(src.dtype).expand(d.shape[:-1]).contiguous()
+
+
+@torch.no_grad()
+def root_follow(joints, parents, source_joints, joint_map=None, root_scale=None, global_trans=None, weights=None):
+    """``retarget``'s root motion: ``k * src[map[0]]_t - joints[0]`` per frame, (T, 3).  ``k = root_scale`` or, if that is None,
+    the summed rest lengths of the rig's live bones (mapped at both ends, ``weights`` > 0 where given, rest and source length > 0)
+    over the same bones' lengths in the source's first frame; 1 where no bone is live.  A root that is not mapped gives
+    ``global_trans`` (zeros if None) instead.  Torch ops on the device of ``joints``, nothing read back."""
+    joints = joints.detach().float()
+    dev, J = joints.device, int(joints.shape[0])
+    src = source_joints.detach().float().to(dev)
+    Js = int(src.shape[-2])
+    clip = src.reshape(-1, Js, 3)
+    m0 = torch.zeros((), dtype=torch.long, device=dev) if joint_map is None else torch.as_tensor(joint_map).to(dev).long().reshape(-1)[0]
+    if root_scale is None:
+        rest = (joints - joints[_virtual_parents(parents, dev)]).norm(dim=-1)
+        d, w = bone_directions(clip[0], parents, joint_map)
+        if weights is not None:
+            w = w * weights.reshape(-1, J)[0]
+        length = d.norm(dim=-1)
+        live = (w > 0) & (rest > 0) & (length > 0)
+        zero = torch.zeros_like(rest)
+        num, den = torch.where(live, rest, zero).sum(), torch.where(live, length, zero).sum()
+        k = torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.ones_like(den))
+    else:
+        k = torch.as_tensor(root_scale, dtype=torch.float32, device=dev)
+    follow = k * clip.index_select(1, m0.clamp(0, Js - 1).reshape(1))[:, 0] - joints[0]
+    keep = torch.zeros_like(follow) if global_trans is None else global_trans.reshape(-1, 3).expand(follow.shape[0], 3)
+    return torch.where((m0 >= 0) & (m0 < Js), follow, keep).contiguous()
+
+
+@torch.no_grad()
+def retarget(skeleton, pose, source_joints, joint_map=None, root_motion="none", root_scale=None, **fit_bones_kw):
+    """A clip of another skeleton's joints -> a pose track of the rig: the T frames are one batch of T independent problems of
+    ``fit_bones`` on the clip's bone directions (``bone_directions``), whatever the source's proportions.
+
+    ``source_joints``: (T, Js, 3) (or (Js, 3): one frame); ``joint_map`` as in ``bone_directions``; ``pose``: the starting pose,
+    (J, 4) shared by the frames or (T, J, 4).  ``root_motion``: "none" keeps ``pose['global_trans']``; "follow" puts the rig's root
+    where the source's is, ``global_trans_t = k * src[map[0]]_t - joints[0]`` (a root that is not mapped keeps the pose's
+    translation), with ``k = root_scale`` or, if that is None, the summed rest lengths of the rig's live bones over the same
+    bones' lengths in the source's FIRST frame (1 where there is none), computed on the device.  Further keywords go to
+    ``fit_bones``; its ``weights`` multiply the mapping's.
+
+    Returns ``fit_bones``'s dict: a (T, J, 4) / (T, 3) track that feeds ``deform_sequence``, ``render_sequence`` and
+    ``run_interpolation`` unchanged, and ``d_nodes`` (T, J, 3) for ``skeleton_overlay``.  Frames are solved independently: nothing
+    smooths across them."""
+    if root_motion not in ("none", "follow"):
+        raise L.RiggsHipError("retarget: root_motion must be 'none' or 'follow', got %r" % (root_motion,))
+    joints, parents = _rig(skeleton)
+    src = L.require_cuda_f32("source_joints", source_joints.detach())
+    directions, weights = bone_directions(src, parents, joint_map)
+    extra = fit_bones_kw.pop("weights", None)
+    if extra is not None:
+        weights = weights * L.require_cuda_f32("weights", extra.detach())
+    gt = pose["global_trans"]
+    if root_motion == "follow":
+        gt = root_follow(joints, parents, src, joint_map, root_scale, L.require_cuda_f32("global_trans", gt.detach()), weights)
+    return fit_bones((joints, parents), {"local_rotation": pose["local_rotation"], "global_trans": gt}, directions, weights=weights,
+                     **fit_bones_kw)
