@@ -372,6 +372,10 @@ int riggs_pose_slerp(int32_t num_segments, int32_t num_frames, int32_t num_quats
  * every launch's tags unique.  With NULL a private copy inside `acts` is cleared by a memset node per call.
  * rot_bias4 (4 floats, may be NULL) is added to every predicted quaternion: the identity bias
  * [1,0,0,0] of skeleton_warp.py:118 folded into the head instead of a separate elementwise op.
+ * skip: -1 (none) .. depth - 1.  With skip == depth - 1 the HEADS read [emb, h]: W_rot / W_tr then have width + emb columns
+ * (a valid configuration of these entries, tests/test_gpu_pose_mlp_f64.py).  torch's PoseMLP module cannot express it — for
+ * depth <= 2 it builds Linear(hidden, ...) heads in front of [emb, h], as the reference does — so riggs_amd.skeleton.PoseMLP keeps
+ * such a module on the torch-op path, which raises the reference's own shape error.
  * ===================================================================== */
 size_t riggs_pose_mlp_acts_floats(int32_t depth, int32_t width, int32_t multires);
 size_t riggs_pose_mlp_sync_bytes(int32_t depth, int32_t width);

@@ -100,9 +100,11 @@ class PoseMLP(nn.Module):
 
     def _fusable(self, t):
         w = self.net[0].out_features
+        # (depth <= 2 puts the skip on the last layer: h is [emb, h] in front of heads built as Linear(hidden, ...) — the torch-op
+        # path below raises the reference's own shape error; the kernels would read width + emb columns per head row)
         return (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 and self.multires > 0 and w <= 256
                 and self.net[0].in_features == 1 + 2 * self.multires and len(self.net) <= 12
-                and all(l.out_features == w for l in self.net))
+                and self.skips[0] < len(self.net) - 1 and all(l.out_features == w for l in self.net))
 
     def c_params(self):
         """The parameters in the order every C entry takes them (_PoseMLPFn._ptrs): ``weight, bias`` per layer, then the rotation
