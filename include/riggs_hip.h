@@ -1065,6 +1065,13 @@ int riggs_fps_sample_rows(int32_t N, int32_t D, int32_t npoint, const float* row
  * {ssim mean, cs mean} of the five MS-SSIM levels and of the piq level (NaN for a level the call did not compute).
  * workspace: riggs_image_metrics_workspace_floats(B, C, H, W) floats, 8-byte aligned.  Every sum is formed in a fixed order in
  * float64: a frame's row does not depend on B or on the other frames.  All launches go on `stream`; nothing synchronises.
+ * Layout of the workspace after the call (a promise: tests/test_gpu_ssim_window_f64.py reads it).  First the per-workgroup partial
+ * sums as float64, level by level (levels 0..4 = the MS-SSIM pyramid, planned whenever min(H, W) > 160; level 5 = the pooled piq
+ * level, absent when f = 1, where level 0 serves): [plane = b * C + c][workgroup = by * tx + bx][4] = {sum ssim_map, sum cs_map,
+ * sum |x - y|, sum (x - y)^2 (the last two on level 0 only, else 0)}, a workgroup being 32 columns x 64 rows of the level's
+ * (h - 10) x (w - 10) outputs.  Then, as float32, the images of levels 1..5 in that order: x's B * C planes, then y's, each (h, w)
+ * with h_l = ceil(h_{l-1} / 2) (likewise w) for l = 1..4 and H / f, W / f for l = 5.  Parts of a level the call did not compute
+ * (want_ms_ssim = 0) are left as they were.
  * Rejected before any HIP call (non-zero status, riggs_last_error): B < 1 or C < 1, a NULL x / y / out / workspace, a workspace
  * that is too small, want_ms_ssim with min(H, W) <= 160, an SSIM level smaller than 11 on a side after pooling.
  * ===================================================================== */
