@@ -54,6 +54,9 @@ const char* riggs_last_error(void);
  *                             launch, nothing that can time out; ~20 launches instead of 2) whatever the network's size: what a
  *                             host re-runs a frame with after the one-launch kernels reported a lost hand-off.  It must not
  *                             change between the forward and the backward of one frame
+ *   "rays_reread"       0     riggs_fit_rays keeps a joint's rays in registers for all iterations (0) or reads them from
+ *                             global memory again in every iteration (1): the same operations, the same bits (NOTES.md has
+ *                             the measurement behind the default)
  * Unknown names fail.  Set them between frames, not while a launch that reads them is being issued from another thread. */
 int riggs_set_option(const char* name, int32_t value);
 int riggs_get_option(const char* name, int32_t* value);
@@ -1364,6 +1367,45 @@ int riggs_fit_bones(int32_t B, int32_t J, const float* joints, const int32_t* pa
                     const float* global_trans_in, const float* directions, const float* weights, const uint8_t* locked,
                     int32_t iterations, int32_t cg_steps, float damping, float max_step, float* local_rot_out,
                     float* global_trans_out, float* d_nodes, float* residual, riggs_stream stream);
+
+/* =====================================================================
+ * Pose fitting to lines and points (csrc/rays.hip; riggs_amd/pose_edit.py: fit_rays, fit_keypoints): every joint may be held to up
+ * to RIGGS_RAYS_MAX LINES (the ray through a camera centre and a 2-D keypoint; the editor's cursor) and to one POINT (a pin:
+ * riggs_fit_pose's target).  riggs_fit_pose's method: Levenberg-Marquardt with the clamped step, the damped normal equations solved
+ * matrix-free by Jacobi-preconditioned conjugate gradients.  The vector from a point to a line has the constant Jacobian
+ * -(I - d d^T) with respect to the point, so riggs_fit_pose's weight s_h^2 becomes a symmetric 3 x 3 metric N_h per joint that does
+ * not depend on the pose; two or more cameras triangulate and fit in one solve, with one camera the depth is held by the damping
+ * alone.  Restated from the published methods, tests/rays_ref.py is the NumPy restatement.  Added symbol: RIGGS_ABI_VERSION is
+ * unchanged.
+ *
+ * joints, parents, B, J (1 .. 256), local_rot_in, global_trans_in, locked, damping, max_step, *extent (always required), relative,
+ * solve_translation, cg_steps and the outputs are riggs_fit_pose's.  0 <= K <= RIGGS_RAYS_MAX rays per joint: origins (B,J,K,3),
+ * directions (B,J,K,3) of any length, ray_weights (B,J,K); all three NULL iff K == 0.  pins (B,J,3) and pin_weights (B,J): both
+ * NULL = no pins (K == 0 needs them).  Per problem and joint h, once: ray k is live iff ray_weights > 0 and 0 < |direction| < inf
+ * (a NaN fails every comparison: off), d = direction / |direction|; the pin is live iff pin_weights > 0 (wp_h, else 0).  Nothing
+ * of a constraint that is not live is read beyond what decides that (the weight, then the direction): a NaN there changes nothing.
+ *   N_h = wp_h I + sum_k w_hk (I - d_hk d_hk^T) (k ascending; 6 floats),  n_h = ((N_xx + N_yy) + N_zz) / 3
+ * `iterations` >= 0 steps of riggs_fit_pose's iteration with
+ *   1  per live ray e_k = v - (d . v) d, v = o_k - posed_h (from the joint to the nearest point of the line); the pin:
+ *      e = pin_h - posed_h; each shortened to max_step on its own; f_h = sum_k w_hk e_k + wp_h e (k ascending, the pin last);
+ *      the right-hand side is J^T f (riggs_fit_pose's up-sweep with f_h in place of s_h r_h)
+ *   3  the moments S0, S1, S2 of n_h, n_h pc, n_h |pc|^2 in place of s_h^2 ...; Minv_tau' = 1 / (extent^2 S0_0 + damping^2)
+ *   4  J p: u_h = (W_h x pc_h - C_h) + extent tau' (no weight);  J^T: F, M over the subtrees of N_h u_h and pc_h x (N_h u_h), with
+ *      (N u)_x = (N_xx u_x + N_xy u_y) + N_xz u_z and so on;  A = J^T N J + damping^2 I
+ * then one more forward kinematics: d_nodes (B,J,3) and residual (B,J) = the largest |e| (not shortened) over the joint's live
+ * constraints, in world units; 0 where it has none.  A locked joint keeps its quaternion bit for bit, as does a joint whose
+ * subtree holds no live constraint.  A line extends behind its origin; what is minimised is the distance to the line (the
+ * reprojection error times depth / focal length), not the pixel error.
+ * One workgroup per problem, all iterations in ONE launch on `stream` (J <= 64: one wave; else 256 threads); no float atomics:
+ * the same inputs give the same bits, and a problem's result does not depend on the rest of the batch.  Does not allocate, read
+ * back or synchronise: legal inside a stream capture.
+ * ===================================================================== */
+#define RIGGS_RAYS_MAX 8
+int riggs_fit_rays(int32_t B, int32_t J, int32_t K, const float* joints, const int32_t* parents, const float* local_rot_in,
+                   const float* global_trans_in, const float* origins, const float* directions, const float* ray_weights,
+                   const float* pins, const float* pin_weights, const uint8_t* locked, int32_t iterations, int32_t cg_steps,
+                   float damping, float max_step, const float* extent, int32_t relative, int32_t solve_translation,
+                   float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual, riggs_stream stream);
 
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);

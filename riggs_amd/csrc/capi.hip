@@ -24,7 +24,8 @@ static constexpr struct OptDef { const char* name; int def, lo, hi; const char* 
     {"fwd_wide_tiles", 256, 0, 65535}, {"fwd_wide_min", 4096, 256, INT32_MAX},
     {"bin_grouped", -1, -1, 1, "-1 (by size), 0 or 1"}, {"color_side_jobs", 1, 0, 1},
     {"preprocess_bwd_lean", -1, -1, 1, "-1 (with cfg.sparse_zero), 0 or 1"}, {"pose_mlp_layered", 0, 0, 1},
-    {"fwd_hist_view_tol", 20, 0, INT32_MAX}, {"lbs_scalar", 0, -1, 1, "-1 (never), 0 (by size) or 1 (always)"}};
+    {"fwd_hist_view_tol", 20, 0, INT32_MAX}, {"lbs_scalar", 0, -1, 1, "-1 (never), 0 (by size) or 1 (always)"},
+    {"rays_reread", 0, 0, 1}};
 static_assert(sizeof(kOpts) / sizeof(kOpts[0]) == OPT_COUNT, "kOpts needs one record per OptId");
 static auto g_opt = [] { struct { int v[OPT_COUNT]; } o{}; for (int i = 0; i < OPT_COUNT; i++) o.v[i] = kOpts[i].def; return o; }();
 int option(int id) { return g_opt.v[id]; }

@@ -12,7 +12,10 @@ NumPy, scipy and two read-backs per mouse event; here it is torch ops that never
 (a reference skeleton, a frame of a clip of joint positions): Levenberg-Marquardt with matrix-free preconditioned conjugate
 gradients in ONE launch of csrc/fit.hip (riggs_fit_pose; tests/fit_ref.py).  ``fit_bones`` gives every BONE a target direction,
 which a skeleton of other proportions can supply (csrc/bones.hip, riggs_fit_bones; tests/bones_ref.py); ``bone_directions`` takes
-the directions from another skeleton's joints and ``retarget`` turns a clip of them into a pose track.  Inference only."""
+the directions from another skeleton's joints and ``retarget`` turns a clip of them into a pose track.  ``fit_rays`` holds every
+joint to LINES in space and / or a point (csrc/rays.hip, riggs_fit_rays; tests/rays_ref.py): ``camera_rays`` turns 2-D keypoints
+into such lines and ``fit_keypoints`` poses the rig from the keypoints of calibrated cameras, or from the editor's cursor.
+Inference only."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,6 +25,7 @@ from . import _lib as L
 from .dual_quaternion import quaternion_multiply
 
 MAX_HANDLES, MAX_JOINTS = L.CONSTANTS["RIGGS_IK_MAX_HANDLES"], 256
+MAX_RAYS = L.CONSTANTS["RIGGS_RAYS_MAX"]
 
 
 # --------------------------------------------------------------------------- the reference's edit step
@@ -462,3 +466,170 @@ def retarget(skeleton, pose, source_joints, joint_map=None, root_motion="none", 
         gt = root_follow(joints, parents, src, joint_map, root_scale, L.require_cuda_f32("global_trans", gt.detach()), weights)
     return fit_bones((joints, parents), {"local_rotation": pose["local_rotation"], "global_trans": gt}, directions, weights=weights,
                      **fit_bones_kw)
+
+
+# --------------------------------------------------------------------------- lines and points: 2-D keypoints, the editor's cursor
+@torch.no_grad()
+def fit_rays(skeleton, pose, origins, directions, weights=None, pins=None, pin_weights=None, locked=None, iterations=32, cg_steps=8,
+             damping=None, max_step=None, solve_translation=False):
+    """Turn the joints of ``pose`` so that every joint comes to lie on its LINES (the ray through a camera centre and a keypoint,
+    the editor's cursor) and / or at its PIN (a point: ``fit_pose``'s target).  Rays and pins mix freely; two or more rays of a
+    joint from different origins triangulate it within the solve.
+
+    ``skeleton``, ``pose``, ``locked``, ``iterations``, ``cg_steps``, ``damping``, ``max_step``, ``solve_translation``, the
+    batching and the defaults are ``fit_pose``'s.  ``origins`` / ``directions``: (J, K, 3) or (B, J, K, 3), 1 <= K <= 8 lines per
+    joint, each through ``origins`` along ``directions`` (any length); ``origins`` may also be (K, 3), shared by all joints and
+    problems (K cameras).  ``weights`` (J, K) or (B, J, K), default 1.  ``pins`` (J, 3) or (B, J, 3) with ``pin_weights`` (J,) or
+    (B, J), default 1 where ``pins`` is given.  ``origins = directions = None`` with pins is ``fit_pose``'s problem (K = 0).
+    A ray counts where its weight is > 0 and its direction is non-zero and finite, a pin where its weight is > 0; a weight <= 0
+    or NaN switches off, and what is switched off is never used: a NaN there changes no bit of the result.  Per-frame cameras of a
+    clip are this function's job (``fit_keypoints`` shares its cameras among the batch): build (B, J, K, 3) rays with
+    ``camera_rays`` per frame.
+
+    The method is ``fit_pose``'s with a symmetric 3 x 3 metric per joint, ``wp I + sum_k w_k (I - d_k d_k^T)``, in place of its
+    scalar weight (include/riggs_hip.h states the iteration, tests/rays_ref.py restates it in NumPy).  Limits: a line extends
+    behind its origin (a line, not a half-line); what is minimised is the distance to the line — the reprojection error times
+    depth / focal length — not the pixel error; with ONE ray per joint the position along the ray is held only by the damping and
+    the starting pose; two-camera problems can have genuine local minima (a near-antipodal pair on a chain); at 64 and more
+    joints 32 iterations have not converged: raise ``iterations``.  Joint limits, orientation targets, smoothing across frames and
+    lens distortion are out of scope.
+
+    Returns ``{'local_rotation', 'global_trans', 'd_nodes', 'residual'}`` as ``fit_pose`` does, with ``residual`` (..., J) the
+    largest distance of the posed joint to one of its live lines or its pin, in world units; 0 where the joint has none.
+
+    One launch of csrc/rays.hip, allocations through torch only, nothing read back: the call can be captured in a
+    ``torch.cuda.graph`` and replayed after the rays, pins and weights changed in place."""
+    if int(cg_steps) < 1:
+        raise L.RiggsHipError("fit_rays: cg_steps must be >= 1, got %r" % (cg_steps,))
+    if (origins is None) != (directions is None):
+        raise L.RiggsHipError("fit_rays: origins and directions come together")
+    if origins is None and weights is not None:
+        raise L.RiggsHipError("fit_rays: weights without rays")
+    if pins is None and pin_weights is not None:
+        raise L.RiggsHipError("fit_rays: pin_weights without pins")
+    if origins is None and pins is None:
+        raise L.RiggsHipError("fit_rays: neither rays nor pins")
+    K = 0
+    if directions is not None:
+        if directions.dim() not in (3, 4) or directions.shape[-1] != 3:
+            raise L.RiggsHipError("directions has shape %s, expected (J, K, 3) or (B, J, K, 3)" % (tuple(directions.shape),))
+        K = int(directions.shape[-2])
+        if not 1 <= K <= MAX_RAYS:
+            raise L.RiggsHipError("fit_rays: %d rays per joint, 1 to %d are supported" % (K, MAX_RAYS))
+        if tuple(origins.shape) != (K, 3) and (origins.dim() not in (3, 4) or tuple(origins.shape[-3:]) != tuple(directions.shape[-3:])):
+            raise L.RiggsHipError("origins has shape %s, expected (%d, 3) or (..., %d, %d, 3) as directions"
+                                  % (tuple(origins.shape), K, directions.shape[-3], K))
+        if weights is not None and (weights.dim() not in (2, 3) or tuple(weights.shape[-2:]) != tuple(directions.shape[-3:-1])):
+            raise L.RiggsHipError("weights has shape %s, expected (..., %d, %d)" % (tuple(weights.shape), directions.shape[-3], K))
+    if pins is not None:
+        if pins.dim() not in (2, 3) or pins.shape[-1] != 3:
+            raise L.RiggsHipError("pins has shape %s, expected (J, 3) or (B, J, 3)" % (tuple(pins.shape),))
+        if pin_weights is not None and (pin_weights.dim() not in (1, 2) or pin_weights.shape[-1] != pins.shape[-2]):
+            raise L.RiggsHipError("pin_weights has shape %s, expected (..., %d)" % (tuple(pin_weights.shape), pins.shape[-2]))
+    joints, parents, J, q, gt, locked, damping, max_step, relative = _problem("fit_rays", skeleton, pose, locked, iterations, damping, max_step)
+    dev = joints.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if K:
+        directions = L.require_cuda_f32("directions", directions.detach())
+        origins = L.require_cuda_f32("origins", origins.detach())
+        weights = L.require_cuda_f32("weights", None if weights is None else weights.detach())
+        if directions.shape[-3] != J:
+            raise L.RiggsHipError("directions has shape %s, expected (%d, K, 3) or (B, %d, K, 3)" % (tuple(directions.shape), J, J))
+        if origins.dim() == 2:
+            origins = origins.expand(J, K, 3)
+    if pins is not None:
+        pins = L.require_cuda_f32("pins", pins.detach())
+        pin_weights = L.require_cuda_f32("pin_weights", None if pin_weights is None else pin_weights.detach())
+        if pins.shape[-2] != J:
+            raise L.RiggsHipError("pins has shape %s, expected (%d, 3) or (B, %d, 3)" % (tuple(pins.shape), J, J))
+    extent = rig_extent(joints)  # (always: the translation unknown is scaled by it)
+    B, batched, full = _batch("fit_rays", q, gt, [(origins, 4), (directions, 4), (weights, 3), (pins, 3), (pin_weights, 2)])
+    qb, gtb = full(q, (J, 4)), full(gt, (3,))
+    ob = db = wb = pb = pwb = None
+    if K:
+        ob, db = full(origins, (J, K, 3)), full(directions, (J, K, 3))
+        wb = torch.ones(B, J, K, **f32) if weights is None else full(weights, (J, K))
+    if pins is not None:
+        pb = full(pins, (J, 3))
+        pwb = torch.ones(B, J, **f32) if pin_weights is None else full(pin_weights, (J,))
+    q_out, gt_out = torch.empty(B, J, 4, **f32), torch.empty(B, 3, **f32)
+    d_nodes, residual = torch.empty(B, J, 3, **f32), torch.empty(B, J, **f32)
+    with torch.cuda.device(dev):
+        L.check(L.lib().riggs_fit_rays(B, J, K, joints.data_ptr(), parents.data_ptr(), qb.data_ptr(), gtb.data_ptr(), L.ptr(ob),
+                                       L.ptr(db), L.ptr(wb), L.ptr(pb), L.ptr(pwb), L.ptr(locked), int(iterations), int(cg_steps),
+                                       damping, max_step, extent.data_ptr(), relative, int(bool(solve_translation)),
+                                       q_out.data_ptr(), gt_out.data_ptr(), d_nodes.data_ptr(), residual.data_ptr(),
+                                       L.stream_ptr()), "riggs_fit_rays")
+    return _solution(batched, q_out, gt_out, d_nodes, residual)
+
+
+def _pinhole(camera, like):
+    """(fx, fy, cx, cy) of ``loss.camera_intrinsics`` and the view's rotation R (3, 3) and translation t (3,) on ``like``'s device,
+    in the reference's row-vector convention: camera-space point = world point @ R + t (csrc/pinhole.h: pinhole_view)."""
+    from .loss import camera_intrinsics
+    V = camera.world_view_transform.detach().to(device=like.device, dtype=torch.float32)
+    return camera_intrinsics(camera), V[:3, :3], V[3, :3]
+
+
+@torch.no_grad()
+def camera_rays(camera, keypoints):
+    """The lines of sight of 2-D keypoints: ``(origin (3,), directions (..., 3))`` for ``keypoints`` (..., 2) as (x, y) =
+    (column, row) in pixels, as ``fit_rays`` takes them.  The inverse of csrc/pinhole.h's rule (column = fx tx / tz + cx,
+    row = fy ty / tz + cy with ``loss.camera_intrinsics(camera)``; t = p @ R + T with ``camera.world_view_transform`` in the
+    reference's row-vector convention): direction = ((x - cx) / fx, (y - cy) / fy, 1) @ R^-1, origin = -T @ R^-1, the camera's
+    centre.  R^-1 is formed from R's cofactors in torch ops on the keypoints' device (CPU tensors work as well): nothing is read
+    back.  No lens distortion."""
+    kp = keypoints.detach().float()
+    if kp.shape[-1] != 2:
+        raise L.RiggsHipError("camera_rays: keypoints has shape %s, expected (..., 2)" % (tuple(kp.shape),))
+    (fx, fy, cx, cy), R, t = _pinhole(camera, kp)
+    cof = torch.stack([torch.linalg.cross(R[1], R[2]), torch.linalg.cross(R[2], R[0]), torch.linalg.cross(R[0], R[1])], dim=1)
+    Rinv = cof / (R[0] * cof[:, 0]).sum()
+    # (element-wise, not a matrix product: the same keypoint gives the same bits whatever the shape it arrives in)
+    x, y = ((kp[..., 0] - cx) / fx)[..., None], ((kp[..., 1] - cy) / fy)[..., None]
+    return -(t[0] * Rinv[0] + t[1] * Rinv[1] + t[2] * Rinv[2]), x * Rinv[0] + y * Rinv[1] + Rinv[2]
+
+
+@torch.no_grad()
+def fit_keypoints(skeleton, pose, cameras, keypoints, weights=None, pins=None, pin_weights=None, **fit_rays_kw):
+    """Pose the rig from 2-D keypoints: ``cameras``, a list of 1 <= C <= 8 calibrated cameras shared by the batch, and
+    ``keypoints`` (C, J, 2) or (B, C, J, 2) as (x, y) = (column, row) in pixels, one per camera and joint.  ``weights`` (C, J) or
+    (B, C, J): the detector's confidences, default 1; a weight <= 0 or NaN means unseen, and an unseen keypoint may hold anything
+    (a NaN there changes no bit).  ``pins`` / ``pin_weights`` and further keywords go to ``fit_rays``: the editor's drag is ONE
+    call with the cursor as the handle joint's keypoint (weight 0 elsewhere) and pins at the current ``d_nodes`` on the joints
+    that stay.  A clip (B = T frames) gives a pose track for ``deform_sequence`` / ``render_sequence``; frames are solved
+    independently.  Cameras that change from frame to frame are ``fit_rays``'s job: build its rays with ``camera_rays``.
+
+    The rays come from ``camera_rays``, the solve is ONE launch of ``fit_rays`` (its limits apply: with one camera the depth is
+    held only by the damping and the starting pose, and the distance to the ray is minimised, not the pixel error).
+
+    Returns ``fit_rays``'s dict plus ``reprojection`` (..., C, J): the pixel distance between each keypoint and csrc/pinhole.h's
+    projection of the returned ``d_nodes``; 0 where the weight is <= 0.  Torch ops on the device, nothing read back: capturable
+    (with the cameras' ``world_view_transform`` already on the device: ``camera.to("cuda")``)."""
+    cameras = list(cameras)
+    kp = L.require_cuda_f32("keypoints", keypoints.detach())
+    C = len(cameras)
+    if not 1 <= C <= MAX_RAYS:
+        raise L.RiggsHipError("fit_keypoints: %d cameras, 1 to %d are supported" % (C, MAX_RAYS))
+    if kp.dim() not in (3, 4) or kp.shape[-3] != C or kp.shape[-1] != 2:
+        raise L.RiggsHipError("keypoints has shape %s, expected (%d, J, 2) or (B, %d, J, 2)" % (tuple(kp.shape), C, C))
+    if weights is not None:
+        weights = L.require_cuda_f32("weights", weights.detach())
+        if weights.dim() not in (2, 3) or tuple(weights.shape[-2:]) != tuple(kp.shape[-3:-1]):
+            raise L.RiggsHipError("weights has shape %s, expected (..., %d, %d)" % (tuple(weights.shape), C, kp.shape[-2]))
+    rays = [camera_rays(cam, kp[..., c, :, :]) for c, cam in enumerate(cameras)]
+    origins = torch.stack([o for o, _ in rays])            # (C, 3)
+    directions = torch.stack([d for _, d in rays], dim=-2)  # (..., J, C, 3)
+    out = fit_rays(skeleton, pose, origins, directions, weights=None if weights is None else weights.transpose(-1, -2),
+                   pins=pins, pin_weights=pin_weights, **fit_rays_kw)
+    posed = out["d_nodes"]
+    per_camera = []
+    for c, cam in enumerate(cameras):
+        (fx, fy, cx, cy), R, t = _pinhole(cam, posed)
+        v = posed[..., 0:1] * R[0] + posed[..., 1:2] * R[1] + posed[..., 2:3] * R[2] + t
+        dx, dy = fx * v[..., 0] / v[..., 2] + cx - kp[..., c, :, 0], fy * v[..., 1] / v[..., 2] + cy - kp[..., c, :, 1]
+        per_camera.append(torch.sqrt(dx * dx + dy * dy))
+    reprojection = torch.stack(per_camera, dim=-2)
+    if weights is not None:
+        reprojection = torch.where(weights > 0, reprojection, torch.zeros_like(reprojection))
+    return dict(out, reprojection=reprojection)
