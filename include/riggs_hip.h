@@ -1407,6 +1407,57 @@ int riggs_fit_rays(int32_t B, int32_t J, int32_t K, const float* joints, const i
                    float damping, float max_step, const float* extent, int32_t relative, int32_t solve_translation,
                    float* local_rot_out, float* global_trans_out, float* d_nodes, float* residual, riggs_stream stream);
 
+/* =====================================================================
+ * Filters along the time axis of a pose track (csrc/track.hip; riggs_amd/track.py: smooth_track, one_euro_track, OneEuroTrack).
+ * Inference only.  B tracks of T frames and J (1 .. RIGGS_TRACK_MAX_JOINTS) joints: rot_in (B,T,J,4) quaternions of any length
+ * (q, -q and s q with s > 0 are one pose), 16-byte aligned; trans_in (B,T,3) or NULL = the translation is not filtered (then
+ * trans_out and trans_weights are NULL too); weights (B,T,J) and trans_weights (B,T) confidences, NULL = all 1.  A rotation sample
+ * is VALID iff its weight > 0 (a NaN fails the comparison) and 0 < |q|^2 < inf in float32 (not zero, NaN or infinite); a
+ * translation sample iff its weight > 0 and its three components are finite.  Every other sample is a GAP: beyond what decides
+ * that, nothing of it enters any output (the one exception is named below).  q^ = q / |q| with |q|^2 = ((w w + x x) + y y) + z z.
+ * Outputs are unit quaternions.  One launch each on `stream`; no float atomics: the same inputs give the same bits, and a track's
+ * result does not depend on the rest of the batch.  Neither allocates, reads back or synchronises: legal inside a stream capture.
+ * Restated from the published methods; tests/track_ref.py is the NumPy restatement.  Added symbols: RIGGS_ABI_VERSION is unchanged.
+ *
+ * riggs_track_smooth: a confidence-weighted Gaussian window on SO(3).  taps (radius + 1) device floats g[d], g[0] first (the caller
+ * evaluates exp(-d^2 / (2 sigma^2)); the kernel evaluates no exp); 0 <= radius <= RIGGS_TRACK_MAX_RADIUS.  The window of frame t is
+ * s = t - radius .. t + radius in that order, clipped to [0, T), or with `wrap` taken modulo T (2 radius + 1 <= T is required).
+ *   support[t,j] = sum_s w,  w = g[|s - t|] c[s,j]   over the window's valid samples (0 where there is none)
+ *   M = sum_s (w q^_a) q^_b   (10 entries, a <= b)   the chordal L2 mean of the rotations is the unit eigenvector of M's largest
+ *   eigenvalue (Markley, Cheng, Crassidis & Oshman 2007); M does not see a sample's sign.  Four cyclic Jacobi sweeps over the
+ *   pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) in registers, no data-dependent exit; per pair theta = (a_qq - a_pp) / (2 a_pq),
+ *   t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) (0 where a_pq = 0), c = 1 / sqrt(t^2 + 1), s = t c.  The column of the largest
+ *   diagonal entry (the first on equality), normalised.  Sign: dot(out, q^_t) >= 0 where sample (t, j) is valid, else the first
+ *   non-zero component is positive.
+ *   trans_out[t] = (sum_s w p_s) / (sum_s w) with w = g[|s - t|] c[s] over the valid translation samples of the same window.
+ * Without support (support = 0) rot_out is the input sample normalised where 0 < |q|^2 < inf - the one place a gap's quaternion is
+ * read - else (1, 0, 0, 0), and trans_out the input row.  radius = 0 returns the normalised input.  One thread per (b, t, j),
+ * adjacent threads on adjacent joints; joint 0's thread filters the frame's translation.
+ *
+ * riggs_track_one_euro: the one-euro filter (Casiez, Roussel & Vogel 2012), causal, one lane per (b, j) over the T frames and one
+ * per track for the translation.  State, read and written in place (a call continues where the last one stopped: T frames in one
+ * call and in two calls are the same code, and the same bits): state_rot (B,J,4) q^, state_omega (B,J), state_gap (B,J) frames
+ * since the last valid sample, < 0 = none yet; state_trans (B,3), state_velocity (B,3), state_trans_gap (B) (NULL iff trans_in is).
+ * A fresh state is state_gap = state_trans_gap = -1 and anything finite elsewhere.  alpha(f, dt) = 1 / (1 + 1 / ((2 pi f) dt)).
+ * Per frame, a valid sample x = q^:  the first one sets q^ = x, omega^ = 0;  otherwise dt = (gap + 1) / rate, x = -x where
+ * dot(x, q^) < 0, th = acos(min(|dot|, 1)), omega = 2 th / dt, a_d = alpha(d_cutoff, dt), omega^ = a_d omega + (1 - a_d) omega^,
+ * a = alpha(min_cutoff + beta omega^, dt), q^ = slerp(q^, x, a) in riggs_pose_slerp's steps from its dot product on (the sin
+ * weights, the linear ones where sin(th) <= 1e-6, the result normalised); gap = 0.  A gap frame keeps the state and raises gap.
+ * rot_out[t] = q^, or (1, 0, 0, 0) before any sample.  The translation likewise on vectors: v = (p - p^) / dt,
+ * v^ = a_d v + (1 - a_d) v^ per component, a = alpha(trans_min_cutoff + trans_beta |v^|, dt), p^ = a p + (1 - a) p^;
+ * trans_out[t] = p^, or 0 before any sample.  rate, min_cutoff, d_cutoff, trans_min_cutoff > 0, beta, trans_beta >= 0, all finite.
+ * ===================================================================== */
+#define RIGGS_TRACK_MAX_RADIUS 64
+#define RIGGS_TRACK_MAX_JOINTS 256
+int riggs_track_smooth(int32_t B, int32_t T, int32_t J, int32_t radius, int32_t wrap, const float* rot_in, const float* trans_in,
+                       const float* weights, const float* trans_weights, const float* taps, float* rot_out, float* trans_out,
+                       float* support, riggs_stream stream);
+int riggs_track_one_euro(int32_t B, int32_t T, int32_t J, const float* rot_in, const float* trans_in, const float* weights,
+                         const float* trans_weights, float rate, float min_cutoff, float beta, float d_cutoff,
+                         float trans_min_cutoff, float trans_beta, float* state_rot, float* state_omega, int32_t* state_gap,
+                         float* state_trans, float* state_velocity, int32_t* state_trans_gap, float* rot_out, float* trans_out,
+                         riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);
