@@ -36,6 +36,41 @@ __device__ __forceinline__ ushort4 unpack_rect(const uint2 w) {
 }
 __device__ __forceinline__ ushort4 load_rect(const ushort4* p) { return unpack_rect(*reinterpret_cast<const uint2*>(p)); }
 
+// two u16 counters in a dword, added half by half (v_pk_add_u16: no carry from the low half into the high one)
+__device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {
+  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b));
+}
+
+// The per-wave cursor table of the tile sort's scatter kernel, u16 rel[W][stride]: the row stride is a multiple of 8 tiles (16
+// bytes) and the table stands at the front of the dynamic LDS, so that it is zeroed 16 bytes at a time and a thread takes FOUR
+// adjacent tiles of a row with one 8-byte access.
+__host__ __device__ __forceinline__ int bin_rel_stride(int T) { return (T + 7) & ~7; }
+// counts -> offsets of the waves inside the block's segment, on packed halves (a chunk adds at most g_per_block <= 16 384 to a
+// tile: no carry crosses a half).  WC > 0: the number of waves is known, every row's counters are asked for before the first add.
+template <int WC>
+__device__ __forceinline__ void rel_counts_to_offsets4(uint2* __restrict__ rel64, int row64 /* uint2 per row */, int W, int tid, int nthr) {
+  for (int q = tid; q < row64; q += nthr) {
+    uint2 r = make_uint2(0u, 0u);
+    if constexpr (WC > 0) {
+      uint2 cw[WC];
+#pragma unroll
+      for (int w = 0; w < WC; w++) cw[w] = rel64[(size_t)w * row64 + q];
+#pragma unroll
+      for (int w = 0; w < WC; w++) {
+        rel64[(size_t)w * row64 + q] = r;
+        r.x = pk_add_u16(r.x, cw[w].x); r.y = pk_add_u16(r.y, cw[w].y);
+      }
+    } else {
+      for (int w = 0; w < W; w++) {
+        const uint2 c = rel64[(size_t)w * row64 + q];
+        rel64[(size_t)w * row64 + q] = r;
+        r.x = pk_add_u16(r.x, c.x); r.y = pk_add_u16(r.y, c.y);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(1024) void bin_count_kernel(int N, int T, int grid_x, int g_per_block,
                                                         const uint32_t* __restrict__ order,
                                                         const ushort4* __restrict__ rect,
@@ -62,37 +97,48 @@ __global__ __launch_bounds__(1024) void bin_count_kernel(int N, int T, int grid_
 }
 
 // per tile: exclusive scan over the chunks, in place; tile_count[t] = total.
-// Workgroup = 64 tiles x 16 chunk segments: every thread sums its segment (loads independent and
-// coalesced across the 64 tiles), LDS prefix over the 16 segments, then the exclusive prefixes are
-// written back — no serial walk over hundreds of chunks.
-#define SCAN_SEG 16
-#define SCAN_KEEP 32
+// Workgroup = TILES tiles x SEGS chunk segments (1024 threads): every thread sums its segment (loads independent and
+// coalesced across the TILES tiles), LDS prefix over the segments, then the exclusive prefixes are
+// written back — no serial walk over hundreds of chunks.  The split is a compile-time pair: fewer tiles per workgroup with
+// more segments puts the same column blocks on more compute units (2500 tiles: 40 workgroups at 64 x 16, 79 at 32 x 32)
+// at shorter row pieces (TILES * 4 bytes); a segment of up to SCAN_CHUNKS / SEGS chunks stays in registers.
+#define SCAN_THREADS 1024
+#define SCAN_CHUNKS 512  // chunks up to which a thread keeps its segment in registers (beyond: the slow path re-reads)
+#ifndef BIN_SCAN_TILES
+#define BIN_SCAN_TILES 64  // tiles (or groups) per workgroup of the tile sort's scan: NOTES.md, "LDS set-up passes of the two sorts"
+#endif
+#ifndef RS_SCAN_TILES
+#define RS_SCAN_TILES 32   // bins per workgroup of the depth sort's scans
+#endif
+template <int TILES>
 __device__ __forceinline__ void bin_scan_body(int T, int n_chunks, uint32_t* __restrict__ table,
                                               uint32_t* __restrict__ tile_count) {
-  __shared__ uint32_t s_seg[SCAN_SEG][64];
-  const int tl = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int t = blockIdx.x * 64 + tl;
-  const int per = (n_chunks + SCAN_SEG - 1) / SCAN_SEG;
+  constexpr int SEGS = SCAN_THREADS / TILES, KEEP = SCAN_CHUNKS / SEGS;
+  static_assert(TILES * SEGS == SCAN_THREADS && KEEP * SEGS == SCAN_CHUNKS && (TILES & (TILES - 1)) == 0, "the split");
+  __shared__ uint32_t s_seg[SEGS][TILES];
+  const int tl = threadIdx.x & (TILES - 1), seg = threadIdx.x / TILES;
+  const int t = blockIdx.x * TILES + tl;
+  const int per = (n_chunks + SEGS - 1) / SEGS;
   const int b0 = seg * per, b1 = min(n_chunks, b0 + per);
   uint32_t sum = 0;
-  if (per <= SCAN_KEEP) {
+  if (per <= KEEP) {
     // the usual case: the whole segment stays in registers (one batch of independent loads, no re-read)
-    uint32_t v[SCAN_KEEP];
+    uint32_t v[KEEP];
 #pragma unroll
-    for (int i = 0; i < SCAN_KEEP; i++) v[i] = (t < T && b0 + i < b1) ? table[(size_t)(b0 + i) * T + t] : 0u;
+    for (int i = 0; i < KEEP; i++) v[i] = (t < T && b0 + i < b1) ? table[(size_t)(b0 + i) * T + t] : 0u;
 #pragma unroll
-    for (int i = 0; i < SCAN_KEEP; i++) sum += v[i];
+    for (int i = 0; i < KEEP; i++) sum += v[i];
     s_seg[seg][tl] = sum;
     __syncthreads();
     uint32_t run = 0;
     for (int s2 = 0; s2 < seg; s2++) run += s_seg[s2][tl];
     if (t < T) {
 #pragma unroll
-      for (int i = 0; i < SCAN_KEEP; i++) {
+      for (int i = 0; i < KEEP; i++) {
         if (b0 + i < b1) table[(size_t)(b0 + i) * T + t] = run;
         run += v[i];
       }
-      if (seg == SCAN_SEG - 1) tile_count[t] = run;
+      if (seg == SEGS - 1) tile_count[t] = run;
     }
     return;
   }
@@ -103,12 +149,13 @@ __device__ __forceinline__ void bin_scan_body(int T, int n_chunks, uint32_t* __r
   for (int s2 = 0; s2 < seg; s2++) run += s_seg[s2][tl];
   if (t < T) {
     for (int b = b0; b < b1; b++) { const uint32_t c = table[(size_t)b * T + t]; table[(size_t)b * T + t] = run; run += c; }
-    if (seg == SCAN_SEG - 1) tile_count[t] = run;
+    if (seg == SEGS - 1) tile_count[t] = run;
   }
 }
-__global__ __launch_bounds__(1024) void bin_scan_kernel(int T, int n_chunks, uint32_t* __restrict__ table,
-                                                        uint32_t* __restrict__ tile_count) {
-  bin_scan_body(T, n_chunks, table, tile_count);
+static inline unsigned bin_scan_grid(int T, int tiles) { return (unsigned)((T + tiles - 1) / tiles); }
+__global__ __launch_bounds__(SCAN_THREADS) void bin_scan_kernel(int T, int n_chunks, uint32_t* __restrict__ table,
+                                                                uint32_t* __restrict__ tile_count) {
+  bin_scan_body<BIN_SCAN_TILES>(T, n_chunks, table, tile_count);
 }
 
 // exclusive scan over the tiles (one workgroup — the extra, last one of bin_scatter_kernel's grid): ranges, checkpoint slot
@@ -261,8 +308,8 @@ __device__ void bin_offsets_body(int T, int64_t cap, const uint32_t* __restrict_
   }
 }
 
-// Scatter.  LDS: s_base[T] (u32 absolute start of this block's segment in each tile) and
-// s_rel[W][T] (u16 offsets of each wave's sub-segment, then used as that wave's running cursor).
+// Scatter.  LDS: s_rel[W][bin_rel_stride(T)] (u16 offsets of each wave's sub-segment, then used as that wave's running cursor)
+// and, behind it, s_base[T] (u32 absolute start of this block's segment in each tile).
 __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int grid_x, int64_t cap, int g_per_block, int g_per_wave,
                                                           const uint32_t* __restrict__ order,
                                                           const ushort4* __restrict__ srect /* rectangles in depth order (bin_count_kernel) */,
@@ -271,7 +318,7 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
                                                           uint32_t* __restrict__ point_list,
                                                           uint32_t* __restrict__ tile_keys, const BinOut out,
                                                           const int n_main, const ColorJob* __restrict__ job_rec, const int job_gpb) {
-  extern __shared__ uint32_t s_mem[];
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
   if ((int)blockIdx.x == n_main) {  // the extra workgroup: what used to be a single-workgroup launch of its own
     bin_offsets_body(T, cap, tile_count, out);
     return;
@@ -284,10 +331,10 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
     return;
   }
   const int W = blockDim.x >> 6;
-  uint32_t* s_base = s_mem;                                            // [T]
-  const int Tpad = (T + 1) & ~1;
-  unsigned short* s_rel = reinterpret_cast<unsigned short*>(s_mem + T);  // [W][Tpad]
-  uint32_t* s_rel32 = s_mem + T;                                        // same storage as packed pairs
+  const int Tpad = bin_rel_stride(T);
+  unsigned short* s_rel = reinterpret_cast<unsigned short*>(s_mem);     // [W][Tpad]
+  uint32_t* s_rel32 = s_mem;                                            // same storage as packed pairs
+  uint32_t* s_base = s_mem + W * (Tpad >> 1);                          // [T]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // a wave walks g_per_wave Gaussians in batches of 64 (one batch in the headline configuration; more when N is large,
   // so that the O(T) set-up of a workgroup — cursor tables, tile bases, its row of the chunk table — is paid per thousands
@@ -319,7 +366,7 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
     cq0[k] = (t < T) ? tile_count[t] : 0u;
     rq0[k] = (t < T) ? row[t] : 0u;
   }
-  for (int e = tid; e < W * (Tpad >> 1); e += blockDim.x) s_rel32[e] = 0u;
+  for (int e = tid; e < W * (Tpad >> 3); e += blockDim.x) reinterpret_cast<uint4*>(s_rel32)[e] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
   ushort4 nx_rc = unpack_rect(nx_w);
   uint32_t nx_n = (uint32_t)((int)(nx_rc.z - nx_rc.x) * (int)(nx_rc.w - nx_rc.y));  // (an absent Gaussian's rectangle is empty)
@@ -337,19 +384,21 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
         }
     }
   }
-  __syncthreads();
   // (ii) counts -> offsets of the waves inside the block's segment; absolute base of the segment = start of the tile's
   // list (every workgroup scans the tile counts itself: T words from L2, instead of a launch that does it once) + the
-  // instances of the earlier chunks
+  // instances of the earlier chunks.
+  // The scan takes FOUR rounds of blockDim tiles per barrier: every wave scans its 64 counts of each round and leaves the four
+  // totals in s_wsum[round][wave]; behind the barrier — the first one is also the one that closes phase (i) — every wave scans
+  // those <= 64 totals itself (lane = (round, wave)) and takes its four offsets from the lanes.  The carry into the next four
+  // rounds is the same sum in every wave: a register.  (A round at a time it was three barriers and a serial loop over the
+  // earlier waves' totals per round: twelve barriers at 2 500 tiles.)  Two buffers: a wave may be a group ahead of another.
   {
-    __shared__ uint32_t s_wsum[16];
-    __shared__ uint32_t s_run;
-    if (tid == 0) s_run = 0u;
-    __syncthreads();
+    __shared__ uint32_t s_wsum[2][64];
+    uint32_t carry = 0u;
     // (the counts and the chunk's row for FOUR rounds of the scan are asked for at once: taken a round at a time — a load, the
     // scan, a barrier, the second load — the workgroup stood through eight dependent round trips at 2 500 tiles)
-    for (int base0 = 0; base0 < T; base0 += 4 * blockDim.x) {
-      uint32_t cq[4], rq[4];
+    for (int base0 = 0, grp = 0; base0 < T; base0 += 4 * blockDim.x, grp ^= 1) {
+      uint32_t cq[4], rq[4], v[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int t = base0 + k * (int)blockDim.x + tid;
@@ -359,34 +408,32 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(int N, int T, int gri
       }
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        const int base = base0 + k * (int)blockDim.x;
-        if (base >= T) break;
-        const int t = base + tid;
-        const uint32_t c = cq[k];
-        uint32_t v = c;
+        v[k] = cq[k];
         for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t u = (uint32_t)__shfl_up((int)v, o);
-          if (lane >= o) v += u;
+          const uint32_t u = (uint32_t)__shfl_up((int)v[k], o);
+          if (lane >= o) v[k] += u;
         }
-        if (lane == 63) s_wsum[wave] = v;
-        __syncthreads();
-        uint32_t off = s_run;
-        for (int w = 0; w < wave; w++) off += s_wsum[w];
-        if (t < T) s_base[t] = off + v - c + rq[k];
-        __syncthreads();
-        if (tid == (int)blockDim.x - 1) s_run = off + v;
-        __syncthreads();
+        if (lane == 63) s_wsum[grp][k * 16 + wave] = v[k];
       }
+      __syncthreads();
+      const uint32_t tot = ((lane & 15) < W) ? s_wsum[grp][lane] : 0u;  // (W <= 16 waves)
+      uint32_t inc = tot;
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
+        if (lane >= o) inc += u;
+      }
+      const uint32_t exc = inc - tot;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int t = base0 + k * (int)blockDim.x + tid;
+        const uint32_t off = carry + (uint32_t)__builtin_amdgcn_readlane((int)exc, k * 16 + wave);
+        if (t < T) s_base[t] = off + v[k] - cq[k] + rq[k];
+      }
+      carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
     }
   }
-  for (int t = tid; t < T; t += blockDim.x) {
-    uint32_t run = 0;
-    for (int w = 0; w < W; w++) {
-      const unsigned short c = s_rel[(size_t)w * Tpad + t];
-      s_rel[(size_t)w * Tpad + t] = (unsigned short)run;
-      run += c;
-    }
-  }
+  if (W == 12) rel_counts_to_offsets4<12>(reinterpret_cast<uint2*>(s_rel32), Tpad >> 2, W, tid, (int)blockDim.x);  // (bin_plan's usual workgroup)
+  else rel_counts_to_offsets4<0>(reinterpret_cast<uint2*>(s_rel32), Tpad >> 2, W, tid, (int)blockDim.x);
   __syncthreads();
   // (iii) ordered walk.  Four Gaussians per step — lanes 4q .. 4q+3 of the wave, q = 0 .. 15 — when their rectangles
   // have at most 16 tiles each (all but ~0 % of the bench scene): lane = (slot, tile of the slot's rectangle).  The
@@ -956,7 +1003,9 @@ __global__ __launch_bounds__(GTS_THREADS, GTS_WAVES) void gbin_tscatter_kernel(i
 struct BinPlan { int g_per_block, g_per_wave, threads, n_chunks; size_t lds_scatter; };
 
 static BinPlan bin_plan(int N, int T) {
-  // LDS of the scatter kernel: T*4 (bases) + W*Tpad*2 (wave cursors) <= ~150 KB
+  // LDS of the scatter kernel: T*4 (bases) + W*Tpad*2 (wave cursors) <= ~150 KB.  (The number of waves — and with it the chunk
+  // size and what an arena must hold — is taken from the rows padded to two tiles, as ever; the kernel pads them to
+  // bin_rel_stride(T), eight: at most 12 bytes more per wave, 192 in all, which the 158 KB asked for below have room for.)
   const int Tpad = (T + 1) & ~1;
   // 12 waves x 64 Gaussians: the ordered walk is a latency chain per wave, so short walks on many waves win;
   // beyond 12 the LDS footprint leaves one workgroup per CU
@@ -973,7 +1022,7 @@ static BinPlan bin_plan(int N, int T) {
   p.g_per_wave = 64 * batches;
   p.g_per_block = W * p.g_per_wave;
   p.n_chunks = (N + p.g_per_block - 1) / p.g_per_block;
-  p.lds_scatter = (size_t)T * 4 + (size_t)W * Tpad * 2;
+  p.lds_scatter = (size_t)T * 4 + (size_t)W * bin_rel_stride(T) * 2;
   return p;
 }
 
@@ -1081,7 +1130,7 @@ int launch_binning(int N, int T, int grid_x, int64_t cap, const uint32_t* order,
     uint4* part_tab = (uint4*)((char*)part_hist + align_up(((size_t)(cap > 0 ? cap : 1) / BIN_PART + (size_t)p.G + 2) * 8 * 4));
     hipLaunchKernelGGL(gbin_count_kernel, dim3(p.n_chunks), dim3(p.W * 64), (size_t)p.W * ((p.G + 1) & ~1) * 2, s, N, T, p.G, p.gxg,
                        p.g_per_block, p.g_per_wave, order, rect, srect, table, wave_start, tile_count);
-    hipLaunchKernelGGL(bin_scan_kernel, dim3((p.G + 63) / 64), dim3(1024), 0, s, p.G, p.n_chunks, table, group_count);
+    hipLaunchKernelGGL(bin_scan_kernel, dim3(bin_scan_grid(p.G, BIN_SCAN_TILES)), dim3(SCAN_THREADS), 0, s, p.G, p.n_chunks, table, group_count);
     // (+ 1: the extra workgroup that lists the second level's parts)
     hipLaunchKernelGGL(gbin_scatter_kernel, dim3(p.n_chunks + 1), dim3(p.W * 64), p.lds, s, N, p.G, p.gxg, cap, p.g_per_block, p.g_per_wave,
                        order, srect, table, wave_start, group_count, inter, part_tab, n_parts);
@@ -1095,13 +1144,13 @@ int launch_binning(int N, int T, int grid_x, int64_t cap, const uint32_t* order,
   uint32_t* table = (uint32_t*)mem;
   uint32_t* tile_count = (uint32_t*)(mem + align_up(((size_t)p.n_chunks + 1) * T * 4));
   ushort4* srect = (ushort4*)((char*)tile_count + align_up((size_t)(T + 1) * 4));
-  if (p.lds_scatter > 150 * 1024) {  // (cannot happen: large tile grids take the grouped path)
+  if (p.lds_scatter > 150 * 1024 + 192) {  // (cannot happen: large tile grids take the grouped path; + 192: the rows' padding, bin_plan)
     set_error("image too large: %d tiles", T);
     return 2;
   }
   hipLaunchKernelGGL(bin_count_kernel, dim3(p.n_chunks), dim3(p.threads), (size_t)T * 4, s, N, T, grid_x, p.g_per_block,
                      order, rect, srect, table);
-  hipLaunchKernelGGL(bin_scan_kernel, dim3((T + 63) / 64), dim3(1024), 0, s, T, p.n_chunks, table, tile_count);
+  hipLaunchKernelGGL(bin_scan_kernel, dim3(bin_scan_grid(T, BIN_SCAN_TILES)), dim3(SCAN_THREADS), 0, s, T, p.n_chunks, table, tile_count);
   // (+ 1: the extra workgroup that writes the ranges, the counters and the forward's work list)
   int n_col = 0, gpb = 0;
   size_t lds = p.lds_scatter;
@@ -1137,6 +1186,28 @@ int launch_binning(int N, int T, int grid_x, int64_t cap, const uint32_t* order,
 #define RS_BIG_MIN_N 1000000
 #endif
 #define RS_SC_WAVES 8   // waves of a scatter workgroup (4 steps of 64 elements each)
+
+// The per-wave cursor tables of the depth sort, tab[ROWS][BINS] u16 (16-byte aligned): a thread owns the EIGHT CONSECUTIVE bins
+// b0 .. b0 + 7 of every row — one 16-byte LDS access per row instead of eight 2-byte ones.
+template <int ROWS, int BINS>
+__device__ __forceinline__ void wave_rows_zero8(unsigned short* tab, int b0) {
+#pragma unroll
+  for (int w = 0; w < ROWS; w++) *reinterpret_cast<uint4*>(tab + w * BINS + b0) = make_uint4(0u, 0u, 0u, 0u);
+}
+// counts -> offsets of the waves inside the chunk's segment: every row's counters are asked for before the first add, the
+// running prefix is four packed dwords (a chunk adds fewer than 2^16 to a bin: see the callers' static assertions)
+template <int ROWS, int BINS>
+__device__ __forceinline__ void wave_rows_counts_to_offsets8(unsigned short* tab, int b0) {
+  uint4 cw[ROWS];
+#pragma unroll
+  for (int w = 0; w < ROWS; w++) cw[w] = *reinterpret_cast<const uint4*>(tab + w * BINS + b0);
+  uint4 r = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+  for (int w = 0; w < ROWS; w++) {
+    *reinterpret_cast<uint4*>(tab + w * BINS + b0) = r;
+    r.x = pk_add_u16(r.x, cw[w].x); r.y = pk_add_u16(r.y, cw[w].y); r.z = pk_add_u16(r.z, cw[w].z); r.w = pk_add_u16(r.w, cw[w].w);
+  }
+}
 
 // routing of a pass: (source, destination) by the "third pass needed" flag (counters[2])
 struct RsBufs {
@@ -1220,10 +1291,10 @@ __global__ __launch_bounds__(CHUNK / 8) void rs_count_kernel(int N, int pass, Rs
 
 // (the third pass's scan when that pass is skipped: bin_scan_kernel itself is shared with the tile binning, so a thin
 // wrapper checks the flag)
-__global__ __launch_bounds__(1024) void rs_scan_kernel(int n_chunks, uint32_t* __restrict__ table, uint32_t* __restrict__ bin_count,
+__global__ __launch_bounds__(SCAN_THREADS) void rs_scan_kernel(int n_chunks, uint32_t* __restrict__ table, uint32_t* __restrict__ bin_count,
                                                        const uint32_t* __restrict__ counters, int pass) {
   (void)counters; (void)pass;
-  bin_scan_body(RS_BINS, n_chunks, table, bin_count);
+  bin_scan_body<RS_SCAN_TILES>(RS_BINS, n_chunks, table, bin_count);
 }
 
 // The THIRD pass (top byte: 256 bins) INSIDE the second pass's scatter launch: it runs only when the depths straddle a
@@ -1242,7 +1313,7 @@ __device__ void rs_third_pass_body(int N, int n_chunks, const RsBufs& bufs, uint
                                    uint32_t* __restrict__ counters, const int G /* participating workgroups: blockIdx.x < G */) {
   __shared__ uint32_t s_hist[RS3_BINS];
   __shared__ uint32_t s_start[RS3_BINS];
-  __shared__ unsigned short s_wave[RS_SC_WAVES][RS3_BINS];
+  __shared__ __attribute__((aligned(16))) unsigned short s_wave[RS_SC_WAVES][RS3_BINS];
   __shared__ int s_fail;
   const uint2* src = bufs.a;
   uint32_t* vd = bufs.v_out;
@@ -1281,7 +1352,7 @@ __device__ void rs_third_pass_body(int N, int n_chunks, const RsBufs& bufs, uint
   }
   // ---- phase B: per chunk, the start of every bin (total over all chunks, part of the earlier ones), then rank and scatter
   for (int chunk = blockIdx.x; chunk < n_chunks; chunk += G) {
-    for (int e = tid; e < RS_SC_WAVES * RS3_BINS / 2; e += NT) reinterpret_cast<uint32_t*>(&s_wave[0][0])[e] = 0u;
+    if (tid >= NT - RS3_BINS / 8) wave_rows_zero8<RS_SC_WAVES, RS3_BINS>(&s_wave[0][0], (tid - (NT - RS3_BINS / 8)) * 8);  // (threads without a column below)
     if (tid < RS3_BINS) {
       uint32_t total = 0, before = 0;
       for (int c = 0; c < n_chunks; c += 4) {
@@ -1323,11 +1394,7 @@ __device__ void rs_third_pass_body(int N, int n_chunks, const RsBufs& bufs, uint
       for (int u = 0; u < 4; u++) { s_start[lane * 4 + u] += run; run += c4[u]; }
     }
     __syncthreads();
-    for (int b = tid; b < RS3_BINS; b += NT) {  // counts -> offsets of the waves inside the chunk's segment
-      unsigned short r = 0;
-#pragma unroll
-      for (int w = 0; w < RS_SC_WAVES; w++) { const unsigned short cw = s_wave[w][b]; s_wave[w][b] = r; r += cw; }
-    }
+    if (tid < RS3_BINS / 8) wave_rows_counts_to_offsets8<RS_SC_WAVES, RS3_BINS>(&s_wave[0][0], tid * 8);  // counts -> offsets of the waves inside the chunk's segment
     __syncthreads();
     unsigned short* cur = s_wave[wave];
 #pragma unroll
@@ -1359,8 +1426,8 @@ __global__ __launch_bounds__(RS_SC_WAVES * 64) void rs_scatter_kernel(int N, int
                                                                       uint32_t* __restrict__ counters,
                                                                       uint32_t* __restrict__ table3 /* = table, for the third pass */,
                                                                       uint32_t* __restrict__ arrivals, int g3) {
-  __shared__ uint32_t s_start[RS_BINS];                      // global start of this chunk's segment in each bin
-  __shared__ unsigned short s_wave[RS_SC_WAVES][RS_BINS];    // per-wave counts -> per-wave running offsets
+  __shared__ __attribute__((aligned(16))) uint32_t s_start[RS_BINS];                      // global start of this chunk's segment in each bin
+  __shared__ __attribute__((aligned(16))) unsigned short s_wave[RS_SC_WAVES][RS_BINS];    // per-wave counts -> per-wave running offsets
   __shared__ uint32_t s_part[RS_SC_WAVES];
   const bool three = counters[2] != 0u;
   const uint2* src; uint2* dst;
@@ -1368,6 +1435,10 @@ __global__ __launch_bounds__(RS_SC_WAVES * 64) void rs_scatter_kernel(int N, int
   const int shift = pass * RS_BITS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NT = RS_SC_WAVES * 64, PER = RS_BINS / NT;   // bins per thread in the scan
+  // (the same eight bins tid * PER .. tid * PER + 7 are the thread's in the scan, the zeroing and the counts -> offsets pass: 16
+  // bytes of every wave's row)
+  static_assert(PER == 8, "a thread's bins are one 16-byte access of a u16 row");
+  static_assert(CHUNK < 65536, "packed 16-bit counters: a chunk adds at most CHUNK to a bin, a wave 64 x STEPS");
   // every global load of the workgroup up front — its row of the chunk table, the bin totals, its elements — so that the
   // scan and the two barriers below run under ONE round trip instead of in front of two more (the compiler keeps loads
   // behind a barrier where it finds them).  The row and the totals first: where the two sources' paths join, the compiler
@@ -1406,7 +1477,7 @@ __global__ __launch_bounds__(RS_SC_WAVES * 64) void rs_scatter_kernel(int N, int
     if (lane >= o) v += u;
   }
   if (lane == 63) s_part[wave] = v;
-  for (int e = tid; e < RS_SC_WAVES * RS_BINS / 2; e += NT) reinterpret_cast<uint32_t*>(&s_wave[0][0])[e] = 0u;
+  wave_rows_zero8<RS_SC_WAVES, RS_BINS>(&s_wave[0][0], tid * PER);
   __syncthreads();
   uint32_t run = v - tsum;
   for (int w = 0; w < wave; w++) run += s_part[w];
@@ -1426,11 +1497,7 @@ __global__ __launch_bounds__(RS_SC_WAVES * 64) void rs_scatter_kernel(int N, int
   }
   __syncthreads();
   // counts -> offsets of the waves inside the chunk's segment
-  for (int b = tid; b < RS_BINS; b += NT) {
-    unsigned short r = 0;
-#pragma unroll
-    for (int w = 0; w < RS_SC_WAVES; w++) { const unsigned short cw = s_wave[w][b]; s_wave[w][b] = r; r += cw; }
-  }
+  wave_rows_counts_to_offsets8<RS_SC_WAVES, RS_BINS>(&s_wave[0][0], tid * PER);
   __syncthreads();
   unsigned short* cur = s_wave[wave];
 #pragma unroll
@@ -1517,7 +1584,7 @@ static int launch_depth_sort_t(int N, const uint32_t* keys_in, uint32_t* keys_ou
   for (int pass = 0; pass < 2; pass++) {
     hipLaunchKernelGGL(rs_count_kernel<CHUNK>, dim3(chunks), dim3(CHUNK / 8), 0, s, N, pass, b, table, block_info, (N + 255) / 256, counters,
                        arrivals);
-    hipLaunchKernelGGL(rs_scan_kernel, dim3((RS_BINS + 63) / 64), dim3(1024), 0, s, chunks, table, bin_count, counters, pass);
+    hipLaunchKernelGGL(rs_scan_kernel, dim3(bin_scan_grid(RS_BINS, RS_SCAN_TILES)), dim3(SCAN_THREADS), 0, s, chunks, table, bin_count, counters, pass);
     // (the table of the 12-bit passes is free again when the third pass starts: chunks x 256 counts fit into it)
     hipLaunchKernelGGL(rs_scatter_kernel<CHUNK>, dim3(chunks), dim3(RS_SC_WAVES * 64), 0, s, N, pass, b, table, bin_count, counters,
                        table, arrivals, chunks < rs3_grid ? chunks : rs3_grid);
