@@ -1458,6 +1458,35 @@ int riggs_track_one_euro(int32_t B, int32_t T, int32_t J, const float* rot_in, c
                          float* state_trans, float* state_velocity, int32_t* state_trans_gap, float* rot_out, float* trans_out,
                          riggs_stream stream);
 
+/* =====================================================================
+ * ARAP handle editing of control nodes (csrc/arap.hip; riggs_amd/arap.py: ARAPDeformer, LapDeform): the drag of the reference's
+ * utils/arap_deform.py, "these M nodes go there" -> positions and rotations of all N nodes.  Inference only.
+ * B drags of ONE handle set over one graph.  verts (N,3) rest positions p0; nn_idx (N,K) neighbour lists, an entry outside [0,N)
+ * is a dropped edge; weight (N,K) edge weights w, 0 on a dropped edge.  A = I - W is the reference's L_opt (A[i][nn[i][k]] = -w_ik).
+ * op (N, op_ld) row-major, 16-byte aligned, op_ld a multiple of 4 with N <= op_ld <= 1024: the operator G whose rows of the
+ * non-handle nodes are the rows of pinv(A_u), A_u = A's non-handle columns, and whose handle rows and columns >= N are zero.
+ * handle_idx (M) distinct nodes; handle_pos (B,M,3) their targets; init_verts (B,N,3) or NULL.
+ *   x_init = p0 with the handles on their targets.  Every solve is in displacement form, x = x_init + G (b - A x_init): a
+ *   direction the handles do not determine (a dropped singular value of A_u) keeps its rest position, and a handle stays on its
+ *   target bit for bit.  Where A_u has full rank this is the reference's lstsq_with_handles(A, b).
+ *   The initial solve (skipped when init_verts is given: x = init_verts as it is) has b = A p0, so b - A x_init = A (p0 - x_init).
+ *   Each of `iterations` (the reference runs 3) rounds, with P_ik = p0_i - p0_j, P'_ik = x_i - x_j over the kept edges j = nn[i][k]:
+ *     S_i = sum_k w_ik P_ik P'_ik^T (float64);  R_i = the proper rotation that maximises tr(R S_i) (Horn's quaternion form,
+ *     csrc/horn_rotation.h: the reference's W U^T with the Kabsch flip), or I where for at least one coordinate axis that
+ *     coordinate of every edge is bit-equal at rest and now (arap_deform.py:133-134; a dropped edge counts as equal), or S = 0;
+ *     b_i = 1/2 sum_k w_ik (R_i + R_j) P_ik;  x = x_init + G (b - A x_init).
+ *   pos_out (B,N,3) = x; quat_out (B,N,4) or NULL = the R of the last round as (w,x,y,z) by matrix_to_quaternion's component rule
+ *   (the best-conditioned candidate, no sign fix), (1,0,0,0) for iterations = 0.
+ * One workgroup per drag, all rounds in ONE launch on `stream`; the 64 partial sums of a row of G meet in a fixed tree and there
+ * are no float atomics: the same inputs give the same bits, and a drag's result does not depend on the rest of the batch.  Does not
+ * allocate, read back or synchronise: legal inside a stream capture.  Added symbol: RIGGS_ABI_VERSION is unchanged.
+ * ===================================================================== */
+#define RIGGS_ARAP_EDIT_MAX_NODES 1024
+#define RIGGS_ARAP_EDIT_MAX_K 16
+int riggs_arap_edit(int32_t B, int32_t N, int32_t K, int32_t M, const float* verts, const int32_t* nn_idx, const float* weight,
+                    const float* op, int32_t op_ld, const int32_t* handle_idx, const float* handle_pos, const float* init_verts,
+                    int32_t iterations, float* pos_out, float* quat_out, riggs_stream stream);
+
 int riggs_prof_count(void);
 const char* riggs_prof_name(int32_t id);
 int riggs_prof_enable(uint32_t mask);

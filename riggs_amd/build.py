@@ -52,6 +52,7 @@ SOURCES = {
     "bones.hip": ["-ffp-contract=off"],  # (tests/bones_ref.py rounds every operation, for fit.hip's reason)
     "rays.hip": ["-ffp-contract=off"],  # (tests/rays_ref.py rounds every operation, for fit.hip's reason)
     "track.hip": ["-ffp-contract=off"],  # (tests/track_ref.py rounds every operation, for ik.hip's reason)
+    "arap.hip": ["-ffp-contract=off"],  # (tests/arap_ref.py rounds every operation, for ik.hip's reason)
     "capi.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -601,6 +601,18 @@ class ControlNodeWarp(NodeGaussians, nn.Module):
         traj = self.nodes[:, None, :3].detach() + nd["d_xyz"]
         return traj.detach(), {k: (v[:, 0] if v is not None else None) for k, v in nd.items()}
 
+    @torch.no_grad()
+    def animation_tool(self, t, use_traj=True, t_samp_num=16):
+        """The editor's drag tool over the nodes at time ``t`` (train_gui.py:204-223): a ``riggs_amd.arap.LapDeform`` whose
+        neighbours are picked by the nodes' ``t_samp_num``-sample trajectory when ``use_traj`` is set, else by their positions at
+        ``t``.  ``tool.deform_arap(handle_idx, handle_pos, return_R=True)[0] - tool.init_pcl`` is ``forward``'s ``node_trans_bias``."""
+        from .arap import LapDeform
+        t = torch.as_tensor(t, dtype=torch.float32, device=self.nodes.device).reshape(-1)[:1]
+        nodes = self.nodes[..., :3].detach()
+        pcl = nodes + self.node_deform(t=self.expand_time(t))["d_xyz"]
+        trajectory = self.get_trajectory(t_samp_num=t_samp_num)[0] if use_traj else None
+        return LapDeform(init_pcl=pcl, K=4, trajectory=trajectory, node_radius=self.node_radius.detach())
+
     def geodesic_distance_floyd(self, cur_node, K=8):
         """All-pairs shortest paths over the K-nearest-neighbour graph of the nodes (Floyd-Warshall on an (M, M) matrix)."""
         M = cur_node.shape[0]
